@@ -24,6 +24,12 @@ steps.  value = frames/s = videos * 81 / (50 * seconds_per_step + measured tiled
 
 N = 1: one video, CFG pair evaluated sequentially.  N >= 2 (even): rank r -> video r//2, CFG branch r%2,
 one RCCL all-gather of the 4.2 MB noise prediction per step inside each pair (weak scaling in videos).
+
+A plain run does only what `value` needs: set-up, W warm-up steps, the K timed steps, the tiled VAE decode (1 warm-up + 1 timed),
+the frame all-gather when N > 1, and the JSON line.  `--full` adds everything else the line has carried: per-launch roofline
+entries (attention, GEMM, VAE convolutions), the self-check digests, the host boundary, config 5 (fp8), data sensitivity, the
+pre-loop units, the same-GPU eager yardstick and the CPU baseline.  `--dump-outputs DIR` writes what the timed path returned
+(DIR/latents.npy, DIR/frames.npy; float32) so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -372,6 +378,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true", help="besides the headline, run every extra leg: per-launch roofline entries, "
+                    "self-check digests, host boundary, config 5, data sensitivity, pre-loop units, eager yardstick, CPU baseline "
+                    "(the --no-* / --*-steps options below select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write their final latents "
+                    "(DIR/latents.npy, [1,16,21,60,104]) and every 10th frame of the timed VAE decode (DIR/frames.npy, [1,3,9,480,832]), "
+                    "float32, rank 0's video")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--fp8", action="store_true", help="BASELINE config 5: block Linears on the fp8_linear contract (e4m3 MFMA)")
     ap.add_argument("--sp", type=int, default=1, help="head-parallel (Ulysses) degree inside each forward: world = videos x 2 x sp "
@@ -393,7 +405,7 @@ def main():
                     "torch-ROCm's own kernels after the timed region, ~35 s; reported as `gpu_eager_yardstick`)")
     ap.add_argument("--no-launch-events", action="store_true", help="do not record the per-launch HIP events behind `roofline` / "
                     "`roofline_gemm` in the timed region (they are then null): measures what those ~900 event pairs per forward cost "
-                    "(profiles/r03/README.md: below 0.1 %)")
+                    "(profiles/r03/README.md: below 0.1 %%)")
     ap.add_argument("--layers", type=int, default=40, help=argparse.SUPPRESS)  # debugging only; 40 = the real model
     ap.add_argument("--sample-offset", type=int, default=0, help=argparse.SUPPRESS)  # tests: the N=1 run of video #k (seeds follow the sample id)
     args = ap.parse_args()
@@ -523,7 +535,8 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     phase("warm-up done, timed region starts")
-    ops.PROFILE_ATTN, ops.PROFILE_GEMM = (None, None) if args.no_launch_events else ([], [])
+    launch_events = args.full and not args.no_launch_events
+    ops.PROFILE_ATTN, ops.PROFILE_GEMM = ([], []) if launch_events else (None, None)
     t0 = time.perf_counter()
     final = run(step_ids, record=True)
     torch.cuda.synchronize()
@@ -534,12 +547,14 @@ def main():
     prof, ops.PROFILE_ATTN = ops.PROFILE_ATTN or [], None
     gprof, ops.PROFILE_GEMM = ops.PROFILE_GEMM or [], None
     step_ms = list(pipe.last_step_ms)           # (ms, is_low_noise) of the timed steps (the config-5 leg below records its own)
-    # ---- self-check of what the timed steps produced: a forward that overflowed would time the same
-    if not bool(torch.isfinite(final.float()).all()):
-        raise SystemExit(f"rank {rank}: non-finite latents after the timed steps")
-    lat_digest = tensor_digest(torch, final)
-    if not (1e-3 < lat_digest["std"] < 1e3):
-        raise SystemExit(f"rank {rank}: degenerate latents after the timed steps: {lat_digest}")
+    # ---- --full: self-check of what the timed steps produced: a forward that overflowed would time the same
+    lat_digest = None
+    if args.full:
+        if not bool(torch.isfinite(final.float()).all()):
+            raise SystemExit(f"rank {rank}: non-finite latents after the timed steps")
+        lat_digest = tensor_digest(torch, final)
+        if not (1e-3 < lat_digest["std"] < 1e3):
+            raise SystemExit(f"rank {rank}: degenerate latents after the timed steps: {lat_digest}")
     # VAE tiled decode of THIS run's latents (GF:733; tile (30,52)/(15,26)), timed after the K steps: 1 warm-up + 1 timed
     # N > 1: the 9 tiles are split over the two ranks of the CFG pair (both hold the final latents) and exchanged
     tgroup = None if cfgp is None else cfgp.pair_group
@@ -552,23 +567,30 @@ def main():
     torch.cuda.synchronize()
     vae_s = time.perf_counter() - tv
     assert tuple(frames.shape) == (1, 3, 81, 480, 832)
-    if not bool(torch.isfinite(frames.float()).all()):
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives: the latents of the last timed step and (a fixed sample of) their decode
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "latents.npy"), final.float().cpu().numpy())                 # 8.4 MB
+        np.save(os.path.join(args.dump_outputs, "frames.npy"), frames[:, :, ::10].float().cpu().numpy())   # frames 0, 10, ..., 80: 43 MB
+        phase(f"outputs written to {args.dump_outputs}")
+    if args.full and not bool(torch.isfinite(frames.float()).all()):
         raise SystemExit(f"rank {rank}: non-finite decoded frames")
     # per-launch events of the decode's convolutions (config 4's roofline entries): a third decode, outside `vae_s`
     vae_roofline, vae_conv_ms = None, None
-    if world == 1 and not args.no_launch_events:
+    if world == 1 and launch_events:
         ops.PROFILE_CONV = []
         vae.decode(final, tiled=True, tile_size=(30, 52), tile_stride=(15, 26))
         torch.cuda.synchronize()
         cprof, ops.PROFILE_CONV = ops.PROFILE_CONV, None
         vae_roofline, vae_conv_ms = vae_entries(cprof)
     u8 = pipe.frames_uint8(frames)                      # [81,480,832,3] uint8, 97 MB (what the reference saves, GF:735)
-    frames_digest = tensor_digest(torch, u8)
+    frames_digest = tensor_digest(torch, u8) if args.full else None
     # ---- the host side of the B1 boundary (N = 1): `pipe(...)` is handed a host control-signal video ([81,480,832,3] bf16, 194 MB; the
     # reference's dataset builds it on the CPU) and an image, and returns 81 PIL frames (97 MB device -> host + the PIL wrapping, UTIL:85-91).
     # `value` is measured with inputs resident in HBM; this is what the PCIe crossings and the PIL conversion add per video.
     host_boundary = None
-    if world == 1:
+    if world == 1 and args.full:
         try:
             hc = torch.zeros((81, 480, 832, 3), dtype=torch.bfloat16).pin_memory()
             hc.to(dev)
@@ -594,7 +616,8 @@ def main():
     # end-of-run all-gather of every sample's frames among the samples' lead ranks (one contributor per sample, the
     # other ranks send nothing): 1 warm-up + 1 timed.  Rank 0 is a lead and ends up with every video's frames.
     gather_s, n_gathered = 0.0, 1
-    sample_digests = [{"sample": sample, "latents_sha256": lat_digest["sha256"], "frames_uint8_sha256": frames_digest["sha256"]}]
+    sample_digests = None if not args.full else \
+        [{"sample": sample, "latents_sha256": lat_digest["sha256"], "frames_uint8_sha256": frames_digest["sha256"]}]
     if cfgp is not None:
         cfgp.gather_frames(u8, tuple(u8.shape), torch.uint8, dev)
         torch.cuda.synchronize()
@@ -605,15 +628,16 @@ def main():
         gather_s = time.perf_counter() - tg
         if cfgp.is_lead:
             n_gathered = len(allf)
-            if not torch.equal(allf[cfgp.sample], u8):
+            if args.full and not torch.equal(allf[cfgp.sample], u8):
                 raise SystemExit(f"rank {rank}: the gathered frames of sample {cfgp.sample} differ from the local decode")
-        # every video's checksums on rank 0: frames from the gathered tensors themselves, latents from their owners
-        lat_all = [None] * world
-        dist.all_gather_object(lat_all, (sample, cfgp.is_lead, lat_digest["sha256"]))
-        if rank == 0:
-            lat_by_sample = {sm: h for sm, lead, h in lat_all if lead}
-            sample_digests = [{"sample": args.sample_offset + i, "latents_sha256": lat_by_sample[args.sample_offset + i],
-                               "frames_uint8_sha256": tensor_digest(torch, f)["sha256"]} for i, f in enumerate(allf)]
+        if args.full:
+            # every video's checksums on rank 0: frames from the gathered tensors themselves, latents from their owners
+            lat_all = [None] * world
+            dist.all_gather_object(lat_all, (sample, cfgp.is_lead, lat_digest["sha256"]))
+            if rank == 0:
+                lat_by_sample = {sm: h for sm, lead, h in lat_all if lead}
+                sample_digests = [{"sample": args.sample_offset + i, "latents_sha256": lat_by_sample[args.sample_offset + i],
+                                   "frames_uint8_sha256": tensor_digest(torch, f)["sha256"]} for i, f in enumerate(allf)]
     phase("frame all-gather done")
     if world > 1:
         t = torch.tensor([elapsed, vae_s, gather_s], device=dev, dtype=torch.float64)
@@ -623,7 +647,7 @@ def main():
     # ---- BASELINE config 5 on the same modules (N = 1, bf16 run only): every block Linear on the fp8_linear contract
     # (VRAM:115-151), 1 warm-up + --config5-steps timed steps spread over the schedule like the bf16 ones
     config5 = None
-    if world == 1 and not args.fp8 and args.config5_steps > 0:
+    if args.full and world == 1 and not args.fp8 and args.config5_steps > 0:
         from goal_force_amd.dit import enable_fp8
         try:
             for m in (dit, dit2, cn, cn2):
@@ -632,7 +656,7 @@ def main():
             ids5 = sorted({min(n_sched - 1, ((2 * i + 1) * n_sched) // (2 * k5)) for i in range(k5)}) if k5 > 1 else [0]
             run([ids5[0]])
             torch.cuda.synchronize()
-            ops.PROFILE_ATTN, ops.PROFILE_GEMM = (None, None) if args.no_launch_events else ([], [])
+            ops.PROFILE_ATTN, ops.PROFILE_GEMM = ([], []) if launch_events else (None, None)
             t5 = time.perf_counter()
             final5 = run(ids5, record=True)
             torch.cuda.synchronize()
@@ -667,7 +691,7 @@ def main():
     # ---- data sensitivity (N = 1, bf16): the same steps with every self-attention's logits x 8 — random-init attention is
     # near-uniform (the friendliest data for the lazy-rescale softmax); trained attention is peaky
     sensitivity = None
-    if world == 1 and not args.fp8 and args.peaky == 1.0 and args.peaky_steps > 0:
+    if args.full and world == 1 and not args.fp8 and args.peaky == 1.0 and args.peaky_steps > 0:
         qn = [blk.self_attn.norm_q.weight for m in (dit, dit2, cn, cn2) for blk in m.modules()
               if hasattr(blk, "self_attn") and hasattr(blk.self_attn, "norm_q")]
         try:
@@ -677,7 +701,7 @@ def main():
             idsp = sorted({min(n_sched - 1, ((2 * i + 1) * n_sched) // (2 * kp)) for i in range(kp)}) if kp > 1 else [0]
             run([idsp[0]])
             torch.cuda.synchronize()
-            ops.PROFILE_ATTN = None if args.no_launch_events else []
+            ops.PROFILE_ATTN = [] if launch_events else None
             finalp = run(idsp, record=True)
             torch.cuda.synchronize()
             profp, ops.PROFILE_ATTN = ops.PROFILE_ATTN or [], None
@@ -704,7 +728,7 @@ def main():
 
     # ---- pre-loop units at full size (N = 1): reported separately, never part of `value`
     preloop = None
-    if world == 1 and not args.no_preloop:
+    if args.full and world == 1 and not args.no_preloop:
         try:
             preloop = preloop_seconds(torch, vae, dev)
         except Exception as e:      # noqa: BLE001
@@ -713,7 +737,7 @@ def main():
 
     # ---- same-GPU yardstick (N = 1, bf16, full depth): the step through torch-ROCm's own kernels, reported beside cpu_baseline
     yardstick = None
-    if world == 1 and not args.fp8 and not args.no_yardstick and args.peaky == 1.0:
+    if args.full and world == 1 and not args.fp8 and not args.no_yardstick and args.peaky == 1.0:
         try:
             yardstick = gpu_eager_yardstick(torch, pipe, cfg, dict(latents=latents, y=y, control=control, ctx_p=ctx_p, ctx_n=ctx_n),
                                             lambda m: print(m, file=sys.stderr, flush=True))
@@ -783,34 +807,35 @@ def main():
                             "collectives": None if world == 1 else "per step: all-gather of the 4.19 MB noise prediction inside each "
                                            "CFG pair; VAE tiles broadcast inside the pair; end of run: all-gather of the uint8 frames (97 MB "
                                            "per sample) among the samples' lead ranks, timed as frame_allgather_s and included in value"},
-            "self_check": {"latents_finite": True, "frames_finite": True, "latents": lat_digest, "frames_uint8": frames_digest,
-                           "per_sample": sample_digests,
-                           "note": "latents = output of the K timed steps of rank 0's sample (finite, std in (1e-3,1e3) or the run "
-                                   "aborts); frames = tiled VAE decode of those latents -> uint8 as the reference saves them"},
             "frames_per_sec_denoise_only": videos * 81.0 / loop_s,
             "denoise_step_ms_high_noise": sum(hi) / len(hi) if hi else None,
             "denoise_step_ms_low_noise": sum(lo) / len(lo) if lo else None,
             "step_mfma_frac": (sum(step_flops) / elapsed / 1e12) / PEAK_BF16_TFLOPS,
             "frames_per_sec_unweighted": videos * 81.0 / (n_sched * sec_per_step + vae_s + gather_s),
-            "roofline": {"bound": "mfma", "kernel": "flash_attn_fwd_kernel3<2> (self-attention, S=32760, 40 heads, d=128; V^T is written by the V projection GEMM, gf_linear_vt32)",
-                         "achieved": achieved, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                         "peak_note": "dense bf16 MFMA peak = 256 CU x 4096 FLOP/clk x 2.4 GHz (MI355X_MICROARCH.md); under this "
-                                      "load the chip holds 1.74-2.05 GHz depending on the box and build (rocprofv3 GRBM_GUI_ACTIVE: 1.84 GHz "
-                                      "at 75 % MFMA-busy in profiles/r03/pmc/attn_SQ.md: 1.87 GHz), i.e. 1.8-2.1 PFLOP/s",
-                         "frac": None if achieved is None else achieved / PEAK_BF16_TFLOPS,
-                         # HBM bytes per launch from rocprofv3 --pmc (separate FETCH_SIZE / WRITE_SIZE passes over
-                         # tools/microbench.py attn, profiles/r01/pmc/): (2 x FETCH_SIZE [gfx950 reports half of a 16-B/lane
-                         # stream] + WRITE_SIZE) KiB -> bytes.  Not collected live: PMC needs the profiler.
-                         # The launch = flash_attn_fwd_kernel3<2> alone (V^T is written by the V projection, gf_linear_vt32).
-                         "traffic": attn_traffic, "traffic_static": True,
-                         "traffic_source": attn_traffic_src,
-                         "algorithmic_bytes_per_launch": 4 * S_TOK * DIM * 2 // args.sp,      # Q + K + V read, O written
-                         "launches": len(self_att), "avg_launch_ms": att_ms if self_att else None,
-                         "algorithmic_flops_per_launch": att_flops},
         }
-        # second entry: the FFN GEMMs (D->F with the GELU epilogue, F->D with gate*+residual) — with the four D->D
-        # projections the GEMMs are the other ~45 % of a step
-        out["roofline_gemm"] = gemm_entries(gprof, S_TOK // args.sp, args.fp8)
+        if args.full:
+            out["self_check"] = {"latents_finite": True, "frames_finite": True, "latents": lat_digest, "frames_uint8": frames_digest,
+                                 "per_sample": sample_digests,
+                                 "note": "latents = output of the K timed steps of rank 0's sample (finite, std in (1e-3,1e3) or the run "
+                                         "aborts); frames = tiled VAE decode of those latents -> uint8 as the reference saves them"}
+            out["roofline"] = {"bound": "mfma", "kernel": "flash_attn_fwd_kernel3<2> (self-attention, S=32760, 40 heads, d=128; V^T is written by the V projection GEMM, gf_linear_vt32)",
+                               "achieved": achieved, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                               "peak_note": "dense bf16 MFMA peak = 256 CU x 4096 FLOP/clk x 2.4 GHz (MI355X data sheet); under this "
+                                            "load the chip holds 1.74-2.05 GHz depending on the box and build (rocprofv3 GRBM_GUI_ACTIVE: 1.84 GHz "
+                                            "at 75 % MFMA-busy in profiles/r03/pmc/attn_SQ.md: 1.87 GHz), i.e. 1.8-2.1 PFLOP/s",
+                               "frac": None if achieved is None else achieved / PEAK_BF16_TFLOPS,
+                               # HBM bytes per launch from rocprofv3 --pmc (separate FETCH_SIZE / WRITE_SIZE passes over
+                               # tools/microbench.py attn, profiles/r01/pmc/): (2 x FETCH_SIZE [gfx950 reports half of a 16-B/lane
+                               # stream] + WRITE_SIZE) KiB -> bytes.  Not collected live: PMC needs the profiler.
+                               # The launch = flash_attn_fwd_kernel3<2> alone (V^T is written by the V projection, gf_linear_vt32).
+                               "traffic": attn_traffic, "traffic_static": True,
+                               "traffic_source": attn_traffic_src,
+                               "algorithmic_bytes_per_launch": 4 * S_TOK * DIM * 2 // args.sp,      # Q + K + V read, O written
+                               "launches": len(self_att), "avg_launch_ms": att_ms if self_att else None,
+                               "algorithmic_flops_per_launch": att_flops}
+            # second entry: the FFN GEMMs (D->F with the GELU epilogue, F->D with gate*+residual) — with the four D->D
+            # projections the GEMMs are the other ~45 % of a step
+            out["roofline_gemm"] = gemm_entries(gprof, S_TOK // args.sp, args.fp8)
         if vae_roofline is not None:
             out["roofline_vae"] = vae_roofline
             out["vae_decode_conv_ms"] = vae_conv_ms
@@ -835,7 +860,7 @@ def main():
         if pre is not None:
             out["preflight"] = {"steps": pre["steps"], "rccl_ranks": pre["rccl_ranks"], "min_hbm_free_gb": pre["min_hbm_free_gb"],
                                 "ranks": [{k_: r[k_] for k_ in ("rank", "sample", "branch", "sp_rank", "device", "hbm_free_gb")} for r in pre["ranks"]]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(torch)
         print(json.dumps(out))
     if world > 1:

@@ -17,8 +17,9 @@ import pytest
 from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
-# the sharding tests time two layers; the extra legs of the N = 1 line (config 5, data sensitivity, pre-loop) have their own test below
-ARGS = ["--layers", "2", "--steps", "2", "--warmup", "0", "--no-cpu-baseline", "--config5-steps", "0", "--peaky-steps", "0", "--no-preloop", "--no-yardstick"]
+# the sharding tests time two layers; the extra legs of the N = 1 line (config 5, data sensitivity, pre-loop) have their own test below.
+# --full: the self-check digests and the roofline entries these tests read are not part of a plain run
+ARGS = ["--full", "--layers", "2", "--steps", "2", "--warmup", "0", "--no-cpu-baseline", "--config5-steps", "0", "--peaky-steps", "0", "--no-preloop", "--no-yardstick"]
 
 
 def _free_port():
@@ -87,7 +88,7 @@ def test_bench_two_ranks_bit_identical_to_one():
 
 # BASELINE config 3's WORKLOAD: the production model — 40 DiT + 10 ControlNet blocks, both experts, S = 32760 — not a
 # two-layer stand-in.  K = 2 puts one timed step on each side of the expert switch (step ids 12 and 37).
-FULL = ["--steps", "2", "--warmup", "0", "--no-cpu-baseline", "--config5-steps", "0", "--peaky-steps", "0", "--no-preloop", "--no-yardstick"]
+FULL = ["--full", "--steps", "2", "--warmup", "0", "--no-cpu-baseline", "--config5-steps", "0", "--peaky-steps", "0", "--no-preloop", "--no-yardstick"]
 
 
 def test_bench_cfg_pair_at_production_size_bit_identical_to_one_gpu():
@@ -165,7 +166,7 @@ def test_bench_self_launch_eight_ranks_and_failure_exit_code():
     """BASELINE config 3's layout (4 videos x CFG pair = 8 ranks) through bench.py itself, self-launched, one block deep over
     gloo on the one GPU of the box: four different videos gathered on rank 0.  And a rank that fails makes the parent exit
     non-zero instead of hanging the others (--sp 3 is refused by every rank)."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--layers", "1", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "8", "--layers", "1", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=_clean_env(), capture_output=True, text=True, timeout=2400)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     j = _one_json(r.stdout)
@@ -225,3 +226,27 @@ def test_bench_head_parallel_pair_bit_identical_to_one_gpu():
     assert [(r["sample"], r["branch"], r["sp_rank"]) for r in sp["preflight"]["ranks"]] == [(0, 0, 0), (0, 0, 1), (0, 1, 0), (0, 1, 1)]
     assert sp["self_check"]["latents"]["sha256"] == one["self_check"]["latents"]["sha256"]
     assert sp["self_check"]["frames_uint8"]["sha256"] == one["self_check"]["frames_uint8"]["sha256"]
+
+
+def test_bench_plain_line_is_lean_and_dumps_the_timed_outputs(tmp_path):
+    """A plain run (no --full) times the steps and the VAE decode and prints the headline only — none of the extra legs — and
+    `--dump-outputs DIR` writes what its timed path returned: the latents are bit for bit the ones the --full run of the same
+    steps reports in `self_check`, and the dump stays under 64 MB."""
+    import hashlib
+
+    import numpy as np
+    import torch
+    one = _launch(1)
+    out = tmp_path / "outputs"
+    j = _launch_now(1, (), ["--layers", "2", "--steps", "2", "--warmup", "0", "--dump-outputs", str(out)])
+    assert j["steps"] == 2 and j["ms_per_step"] > 0 and j["value"] > 0 and j["higher_is_better"] is True
+    assert (j["metric"], j["unit"], j["dtype"]) == (one["metric"], one["unit"], one["dtype"])
+    for leg in ("self_check", "roofline", "roofline_gemm", "roofline_vae", "config5", "data_sensitivity", "preloop", "host_boundary",
+                "gpu_eager_yardstick", "cpu_baseline"):
+        assert leg not in j, f"a plain run carries `{leg}`"
+    lat, frames = np.load(out / "latents.npy"), np.load(out / "frames.npy")
+    assert lat.dtype == np.float32 and lat.shape == (1, 16, 21, 60, 104)
+    assert frames.dtype == np.float32 and frames.shape == (1, 3, 9, 480, 832) and np.isfinite(frames).all()
+    raw = torch.from_numpy(lat).to(torch.bfloat16).view(torch.int16).numpy().tobytes()
+    assert hashlib.sha256(raw).hexdigest() == one["self_check"]["latents"]["sha256"]
+    assert sum(f.stat().st_size for f in out.iterdir()) <= 64e6

@@ -4,7 +4,7 @@ set -u
 OUT=$PWD/gpurun_out/r02b
 mkdir -p $OUT
 export TMPDIR=/tmp
-python3 bench.py > $OUT/bench_default.json.log 2> $OUT/bench_default.err
+python3 bench.py --full > $OUT/bench_default.json.log 2> $OUT/bench_default.err
 rocprofv3 --kernel-trace --stats -d $OUT/trace -o bench -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline > $OUT/bench_steps1.json.log 2> $OUT/trace.err
 python3 tools/rocpd_table.py $OUT/trace/bench_results.db 40 > $OUT/bench_steps1_by_kernel_and_grid.md 2>> $OUT/trace.err
 for c in FETCH_SIZE WRITE_SIZE; do
