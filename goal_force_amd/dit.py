@@ -348,6 +348,40 @@ class CrossAttention(nn.Module):
         ops.rmsnorm_rope(q, self.norm_q.weight, None, None, self.head_dim, self.norm_q.eps)
         return ops.flash_attn(q, kv[0], kv[1], self.num_heads, last_key_mult=kv[2] if len(kv) > 2 else 1)
 
+    # The output projection folded into the cached values: per head the attention output is a mix of the n_keys value
+    # rows, so o(a) = sum_h P_h (V_h W_o,h^T) + b — probabilities [S, H*n_pad] times a table U [D, H*n_pad] that is constant per
+    # (expert, prompt, block) like K / V: K = H*n_pad instead of D in the projection GEMM (1920 instead of 5120 for a 40-token prompt).
+    # n_pad = n_keys + 1 (the last key's rounding residue, ops.cross_probs) rounded up to 16: 48 for a 40-token prompt (41 keys).
+    # FOLD_K_MAX: the largest H*n_pad the folded path takes — every shape gf_cross_probs accepts (n_keys <= 63, K <= 2560 at 40 heads)
+    # measured faster than attention + D->D GEMM (EXPERIMENTS.md, profiles/r07/crossover.log).
+    FOLD_K_MAX = 2560
+
+    def fold_ok(self, kv) -> bool:
+        """Does the folded path serve this (inference) forward: pad-folded keys (multiplicity > 1) few enough for one key tile,
+        a bf16 o projection (not the fp8_linear contract), no autograd, a GEMM-able K (heads x n_pad a multiple of 64: not the
+        2-head test models), ops.options(fold_cross_o) on."""
+        if not ops._OPT["fold_cross_o"] or torch.is_grad_enabled() or len(kv) < 3 or kv[2] == 1 or self.head_dim != 128:
+            return False
+        if getattr(self.o, "_gf_w8", None) is not None:
+            return False
+        n = kv[0].shape[0]
+        k = self.num_heads * self.fold_pad(n)          # the projection GEMM's K: a multiple of 64 (gf_gemm_bf16)
+        return n <= ops.CROSS_FOLD_MAX_KEYS and k <= self.FOLD_K_MAX and k % 64 == 0
+
+    @staticmethod
+    def fold_pad(n_keys: int) -> int:
+        return -(-(n_keys + 1) // 16) * 16
+
+    def fold_table(self, kv):
+        """U = V_h W_o,h^T per head, [D, H*n_pad] bf16 (ops.cross_fold_table): model_fn memoises it in ContextCache beside the K / V."""
+        return ops.cross_fold_table(kv[1], self.o.weight, self.num_heads, self.fold_pad(kv[0].shape[0]))
+
+    def attend_probs(self, x2, kv):
+        """attend() up to the normalised probabilities [S, H*n_pad] (ops.cross_probs) — the A operand of the folded projection."""
+        q = linear(x2, self.q)
+        ops.rmsnorm_rope(q, self.norm_q.weight, None, None, self.head_dim, self.norm_q.eps)
+        return ops.cross_probs(q, kv[0], self.num_heads, self.fold_pad(kv[0].shape[0]), last_key_mult=kv[2])
+
     def forward(self, x: torch.Tensor, y: torch.Tensor):
         x2 = _tokens2d(x)
         a = self.attend(x2, self.context_kv(_tokens2d(y)))
@@ -431,8 +465,14 @@ class DiTBlock(nn.Module):
             ops.layernorm_modulate(x_new, weight=self.norm3.weight, bias=self.norm3.bias, eps=self.eps, out=h)
         if context_kv is None:
             context_kv = self.cross_attn.context_kv(_tokens2d(context), fold=fold_pad_keys and keep is None, pad_n=pad_n)
-        a = self.cross_attn.attend(h, context_kv)
-        linear(a, self.cross_attn.o, epilogue=ops.EPI_BIAS_RESID, resid=x_new, out=x_new)               # DIT:227
+        ca = self.cross_attn
+        if keep is None and not fp8 and ca.fold_ok(context_kv):
+            # the o projection folded into the values: P [S, H*n_pad] @ U^T (context_kv[3] is the table model_fn memoised, if any)
+            u = context_kv[3] if len(context_kv) > 3 else ca.fold_table(context_kv)
+            ops.gemm(ca.attend_probs(h, context_kv), u, ca.o.bias, epilogue=ops.EPI_BIAS_RESID, resid=x_new, out=x_new)  # DIT:227
+        else:
+            a = ca.attend(h, context_kv)
+            linear(a, ca.o, epilogue=ops.EPI_BIAS_RESID, resid=x_new, out=x_new)                        # DIT:227
         if keep is not None and keep.get("wide"):
             keep["x2b"] = x_new.clone()
         if fp8:

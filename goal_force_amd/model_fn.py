@@ -14,8 +14,10 @@ Differences that do not change results:
     `elide_zero_controlnet=False`;
   * `use_unified_sequence_parallel` / `sequence_parallel=` run the blocks on this rank's token chunk with head-parallel
     attention (sequence_parallel.py); unlike the reference's USP path the ControlNet tokens are sharded too;
-  * `context_cache` (optional) memoises text_embedding(context) and the per-block cross-attention K/V,
-    which are constant over the denoising steps for one (expert, prompt);
+  * `context_cache` (optional) memoises text_embedding(context) and the per-block cross-attention K/V, which are constant
+    over the denoising steps for one (expert, prompt) — and so is the folded value table of the cross-attention's o projection
+    (dit.CrossAttention.fold_table).  That fold is the one difference here that moves bf16 roundings: the same
+    function, evaluated as probabilities x (V W_o^T) instead of (attention output) x W_o^T;
   * `cfg_shared` (optional, a dict owned by the caller for ONE denoising step): the cond and the uncond forward of a step differ
     only in the text context, which first enters a block at its cross-attention — the self-attention half of block 0 of the DiT
     and of the ControlNet sees identical inputs in both.  The first forward of the step stores those two tensors in the dict,
@@ -41,6 +43,10 @@ class ContextCache:
         self.pad_n = None       # dit.pad_run(ctx): where the run of identical padded rows starts — detected once, used by every block
         self.dit_kv = {}
         self.cn_kv = {}
+        # the cross-attention's folded value tables U = V_h W_o,h^T (dit.CrossAttention.fold_table), [D, H*n_pad] bf16 per block:
+        # 19.7 MB at 41 keys, ~1 GB per (expert, prompt) over 40 DiT + 10 ControlNet blocks
+        self.dit_u = {}
+        self.cn_u = {}
 
 
 def _unsupported(name, value, default=None):
@@ -140,12 +146,17 @@ def model_fn_wan_video(
     else:
         n_cn = 0
 
-    def kv_for(cache_dict, block, idx):
+    def kv_for(cache_dict, u_dict, block, idx):
         if context_cache is None:
             return None
         if idx not in cache_dict:
             cache_dict[idx] = block.cross_attn.context_kv(ctx[0], pad_n=pad_n)
-        return cache_dict[idx]
+        kv = cache_dict[idx]
+        if block.cross_attn.fold_ok(kv):          # (k, v, m, U): the block takes the folded o projection with the memoised table
+            if idx not in u_dict:
+                u_dict[idx] = block.cross_attn.fold_table(kv)
+            kv = kv + (u_dict[idx],)
+        return kv
 
     # blocks (GF:1503-1570); ControlNet block i is evaluated right before DiT block i
     for block_id, block in enumerate(dit.blocks):
@@ -154,9 +165,11 @@ def model_fn_wan_video(
             memo_cn, memo_dit = cfg_shared.setdefault("cn0", {}), cfg_shared.setdefault("dit0", {})
         if block_id < n_cn:
             cb = controlnet.controlnet_dit.blocks[block_id]
-            c = cb(c, ctx, t_mod, rope, context_kv=kv_for(context_cache.cn_kv if context_cache else None, cb, block_id),
+            c = cb(c, ctx, t_mod, rope, context_kv=kv_for(context_cache.cn_kv if context_cache else None,
+                                                          context_cache.cn_u if context_cache else None, cb, block_id),
                    sp=sp, self_attn_memo=memo_cn, pad_n=pad_n)
-        x = block(x, ctx, t_mod, rope, context_kv=kv_for(context_cache.dit_kv if context_cache else None, block, block_id),
+        x = block(x, ctx, t_mod, rope, context_kv=kv_for(context_cache.dit_kv if context_cache else None,
+                                                         context_cache.dit_u if context_cache else None, block, block_id),
                   sp=sp, self_attn_memo=memo_dit, pad_n=pad_n)
         if block_id < n_cn:
             # x = x + zero_conv(state)   (GF:1565-1570) — Conv1d(k=1) == Linear, fused residual epilogue

@@ -209,9 +209,12 @@ VT_MIN_KV = 2048   # key sequences at least this long go through the pre-transpo
 #                conv_padded (False: the VAE's 192 / 384-channel 3x3x3 convolutions on gf_conv3d_bf16 instead of the padded-layout kernel),
 #                fold_pad_keys (False: cross-attention over all 512 context keys instead of the prompt + ONE key of multiplicity, dit.py),
 #                attn_q_prescale (False: the self-attention's Q is rotated plainly and scaled inside the attention kernel — a second bf16 rounding),
-#                vae_attn_offset (False: the VAE attention's softmax on the bf16-rounded RAW scores — one GEMM instead of two, coarser)
+#                vae_attn_offset (False: the VAE attention's softmax on the bf16-rounded RAW scores — one GEMM instead of two, coarser),
+#                fold_cross_o (False: the cross-attention's output projection as attention + D->D GEMM instead of probabilities x the
+#                              folded value table, dit.CrossAttention.fold_ok)
 _LIB_DEFAULTS = {"prefer_8wave": 0, "a4_stagger": 2, "a4_group_m": 0, "conv_nb": 0, "conv_gather": 0, "conv_direct": 1, "vae_rms3": 1}
-_OPT = {"attn_k3": True, "vt_from_gemm": True, "conv_padded": True, "fold_pad_keys": True, "attn_q_prescale": True, "vae_attn_offset": True}
+_OPT = {"attn_k3": True, "vt_from_gemm": True, "conv_padded": True, "fold_pad_keys": True, "attn_q_prescale": True, "vae_attn_offset": True,
+        "fold_cross_o": True}
 
 
 def lib_option(name: str) -> int:
@@ -383,6 +386,51 @@ def flash_attn(q, k, v, num_heads, out=None, scale=None, vt=None, last_key_mult=
         e1.record()
         prof.append((e0, e1, sq, skv, num_heads))
     return out
+
+
+CROSS_FOLD_MAX_KEYS = 63   # gf_cross_probs holds a row's keys and the last key's residue column in one 64-key tile
+
+
+def cross_probs(q, k, num_heads, n_pad, last_key_mult=1, scale=None, out=None):
+    """The normalised probabilities of softmax(q k^T / sqrt(d)) per head instead of the attention output (gf_cross_probs):
+    q [Sq, H*128], k [n_keys <= 63, H*128] (row-strided views OK) -> [Sq, H*n_pad] bf16 (n_pad > n_keys), column h*n_pad + j = key j
+    of head h; column n_keys: the last key's rounding residue bf16(w - bf16(w)); zero after it.  `last_key_mult` as in flash_attn.  With U = cross_fold_table(v, w_o, H, n_pad), P @ U^T = flash_attn(q, k, v) @ w_o^T."""
+    for n, t in (("q", q), ("k", k)):
+        _req(t, f"cross_probs.{n}")
+        if t.dim() != 2 or t.stride(1) != 1:
+            raise GoalForceError(f"cross_probs.{n}: expected 2-D [len, heads*head_dim] with contiguous rows")
+    sq, hd_all = q.shape
+    n_keys = k.shape[0]
+    head_dim = hd_all // num_heads
+    if k.shape[1] != hd_all or head_dim * num_heads != hd_all:
+        raise GoalForceError("cross_probs: q/k shape mismatch")
+    if out is None:
+        out = torch.empty((sq, num_heads * n_pad), dtype=_BF16, device=q.device)
+    elif out.dtype != _BF16 or out.dim() != 2 or out.stride(1) != 1 or tuple(out.shape) != (sq, num_heads * n_pad):
+        raise GoalForceError(f"cross_probs.out: expected [{sq}, {num_heads * n_pad}] bf16 with contiguous rows")
+    if scale is None:
+        scale = 1.0 / math.sqrt(head_dim)
+    _lib.check(_lib.load().gf_cross_probs(_ptr(q), _ptr(k), _ptr(out), sq, n_keys, n_pad, num_heads, head_dim, q.stride(0), k.stride(0),
+                                          out.stride(0), float(scale), float(last_key_mult), _stream(q)), "gf_cross_probs")
+    return out
+
+
+def cross_fold_table(v, w_o, num_heads, n_pad):
+    """The value table of cross_probs (gf_cross_fold_table): U [N, H*n_pad] bf16, U[n, h*n_pad + j] = sum_d v[j, h*128+d] w_o[n, h*128+d]
+    (fp32 accumulation, one rounding) for j < n_keys, column n_keys = column n_keys - 1 (the partner of cross_probs' residue column),
+    zero after it — the [N, K] weight layout gemm takes."""
+    for n, t in (("v", v), ("w_o", w_o)):
+        _req(t, f"cross_fold_table.{n}")
+        if t.dim() != 2 or t.stride(1) != 1:
+            raise GoalForceError(f"cross_fold_table.{n}: expected 2-D with contiguous rows")
+    n_keys, hd_all = v.shape
+    if w_o.shape[1] != hd_all or hd_all % num_heads:
+        raise GoalForceError("cross_fold_table: v / w_o shape mismatch")
+    N = w_o.shape[0]
+    u = torch.empty((N, num_heads * n_pad), dtype=_BF16, device=v.device)
+    _lib.check(_lib.load().gf_cross_fold_table(_ptr(v), _ptr(w_o), _ptr(u), n_keys, n_pad, num_heads, hd_all // num_heads, N, v.stride(0),
+                                               w_o.stride(0), u.stride(0), _stream(v)), "gf_cross_fold_table")
+    return u
 
 
 def flash_attn_lse(q, k, v, num_heads, scale=None):

@@ -183,6 +183,24 @@ GF_API int gf_flash_attn_fwd_lastmult(const void* q, const void* k, const void* 
                                       int64_t heads, int64_t head_dim, int64_t q_stride, int64_t k_stride, int64_t v_stride,
                                       int64_t o_stride, float scale, float last_key_multiplicity, void* stream);
 
+/* gf_cross_probs — the normalised softmax probabilities of a cross-attention over n_keys < 64 keys, instead of its output:
+ * p[s, h*n_pad + j] = bf16(w_hj), w_hj = softmax_j(scale * q_h . k_hj), the last key (row n_keys - 1) counting `last_key_multiplicity`
+ * times as in gf_flash_attn_fwd_lastmult, the same fp32 score arithmetic.  Column n_keys holds the last key's rounding residue
+ * bf16(w - bf16(w)) (its partner is column n_keys of the table, a copy of column n_keys - 1); columns n_keys < j < n_pad (n_pad > n_keys,
+ * a multiple of 16, <= 64) are written as zeros.  With U from gf_cross_fold_table the attention output times W_o^T is ONE GEMM p @ U^T (K = heads * n_pad):
+ * the cross-attention's output projection folded into the cached values.  q [q_len, heads*128], k [n_keys, heads*128] row-strided,
+ * 16-byte aligned; p [q_len, p_stride >= heads*n_pad] bf16, 8-byte aligned, p_stride a multiple of 4. */
+GF_API int gf_cross_probs(const void* q, const void* k, void* p, int64_t q_len, int64_t n_keys, int64_t n_pad, int64_t heads,
+                          int64_t head_dim, int64_t q_stride, int64_t k_stride, int64_t p_stride, float scale,
+                          float last_key_multiplicity, void* stream);
+
+/* gf_cross_fold_table — the value table of gf_cross_probs: u[n, h*n_pad + j] = bf16(sum_d v[j, h*128 + d] * w_o[n, h*128 + d]) for
+ * n < n_out and j < n_keys (fp32 accumulation, one rounding), column n_keys = column n_keys - 1, zeros for n_keys < j < n_pad.  v [n_keys, heads*128], w_o [n_out, heads*128] (the
+ * o projection's weight) row-strided, 16-byte aligned; u [n_out, u_stride >= heads*n_pad] bf16 — the [N, K] weight layout of
+ * gf_gemm_bf16. */
+GF_API int gf_cross_fold_table(const void* v, const void* w_o, void* u, int64_t n_keys, int64_t n_pad, int64_t heads, int64_t head_dim,
+                               int64_t n_out, int64_t v_stride, int64_t w_stride, int64_t u_stride, void* stream);
+
 /* ------------------------------------------------------------------------
  * Training (ControlNet training step): training_loss (GF:180-193) calls loss.backward() through
  * F.scaled_dot_product_attention (DIT:28-61) in every block.
