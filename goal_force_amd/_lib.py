@@ -29,12 +29,13 @@ SYMBOLS = (
     "gf_conv3d_bf16", "gf_conv3d_padded_bf16", "gf_vae_rmsnorm_silu_padded", "gf_vae_upsample2x_padded", "gf_gemm_bf16_batched", "gf_transpose_pad_batched",
     "gf_resize_lanczos4_u8", "gf_resize_area_u8", "gf_canny_u8", "gf_flash_attn_fwd_lastmult",
     "gf_cross_probs", "gf_cross_fold_table",
+    "gf_sage_workspace_bytes", "gf_sage_k_mean", "gf_sage_quant_q", "gf_sage_quant_k", "gf_sage_quant_vt", "gf_sage_attn_fwd", "gf_sage_attn",
 )
 
 # the C ABI revision these bindings were written against (csrc/gf_abi.hip: GF_ABI_VERSION).  A stale or foreign .so whose entry
 # points take differently sized buffers (gf_flash_attn_bwd's workspace grew 3x between revisions 7 and 10 under an unchanged
 # signature) is refused at load time instead of overrunning memory.
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 EPI_BIAS, EPI_BIAS_GELU_TANH, EPI_BIAS_GATE_RESID, EPI_BIAS_RESID, EPI_BIAS_SILU, EPI_BIAS_MUL = range(6)
 
@@ -121,6 +122,13 @@ def _declare(lib):
         "gf_resize_lanczos4_u8": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp],
         "gf_resize_area_u8": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _int, _vp],
         "gf_canny_u8": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _int, _int, _int, _vp],
+        "gf_sage_workspace_bytes": [_i64] * 3,
+        "gf_sage_k_mean": [_vp, _i64, _vp, _vp, _i64, _i64, _vp],
+        "gf_sage_quant_q": [_vp, _i64, _vp, _vp, _i64, _i64, _vp],
+        "gf_sage_quant_k": [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp],
+        "gf_sage_quant_vt": [_vp, _i64, _int, _vp, _vp, _vp, _i64, _i64, _vp],
+        "gf_sage_attn_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32, _vp],
+        "gf_sage_attn": [_vp, _i64, _vp, _i64, _vp, _i64, _int, _vp, _i64, _i64, _i64, _i64, _f32, _vp, _vp],
     }
     for name, argtypes in sigs.items():
         fn = getattr(lib, name)

@@ -5,7 +5,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#define GF_ABI_VERSION 19
+#define GF_ABI_VERSION 20
 
 static thread_local char g_err[512] = "";
 

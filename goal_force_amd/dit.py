@@ -101,7 +101,8 @@ def sinusoidal_embedding_1d(dim, position):
 def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_heads: int, compatibility_mode=False):
     """DIT:28-61 — q, k, v [B, S, num_heads * head_dim] (`b s (n d)`) -> [B, Sq, num_heads * head_dim]: softmax(q k^T / sqrt(d)) v
     per head, no mask, on the HIP flash-attention kernels (gf_flash_attn_fwd).  `compatibility_mode` only chooses among the
-    reference's backends (flash-attn 3 / 2, sageattention, torch SDPA); there is one backend here, so it is accepted and ignored.
+    reference's backends (flash-attn 3 / 2, sageattention, torch SDPA) and is accepted and ignored here; the sageattention branch is
+    `sageattn` below (bound into the reference) and `enable_sage_attention` for the package's own blocks.
     The q handed in is final (already rounded to bf16 by its producer), so long key sequences run on the kernel that scales the fp32
     scores — SDPA's precision at peaky logits — not on the one that pre-scales and re-rounds Q (ops.flash_attn: finished_q); the
     package's own blocks produce a pre-scaled q instead and keep the faster kernel (SelfAttention.attend)."""
@@ -200,6 +201,46 @@ def enable_fp8(module: nn.Module, enabled=True):
 
 
 
+def enable_sage_attention(module: nn.Module, enabled=True):
+    """The reference's SageAttention branch of flash_attention (DIT:22-26, 50-54: `sageattn(q, k, v)` when the package is installed):
+    every SelfAttention inside the DiT / ControlNet blocks of `module` (a WanModel, a ControlNet, a block or a whole pipeline) runs
+    ops.sage_attn — smoothed-K int8 QK^T, e4m3 PV, fp32 accumulation — on one GPU (bf16 or fp8 linears) and under head
+    parallelism.  Cross-attention stays on the exact kernels; training refuses a switched block (there is no backward).
+    enabled=False restores the flash-attention path bit for bit."""
+    for blk in module.modules():
+        if isinstance(blk, DiTBlock):
+            blk.self_attn._gf_sage = bool(enabled)
+    return module
+
+
+def sageattn(q, k, v, tensor_layout="HND", is_causal=False, sm_scale=None, return_lse=False, **kw):
+    """Drop-in for `sageattention.sageattn` as the reference calls it (DIT:50-54): q, k, v [B, heads, S, 128] ("HND", the strided
+    `rearrange(q, "b s (n d) -> b n s d")` views are fine) or [B, S, heads, 128] ("NHD") bf16 -> the same layout, on
+    ops.sage_attn.  sm_scale defaults to 1/sqrt(128).  Causal masks, the log-sum-exp output and head_dim != 128 are refused; the
+    package's other keywords (quantisation granularities, accumulator types) are accepted and ignored: the recipe here is fixed."""
+    if is_causal:
+        raise GoalForceError("sageattn: is_causal=True is not supported (the Wan DiT attention is non-causal)")
+    if return_lse:
+        raise GoalForceError("sageattn: return_lse=True is not supported")
+    if tensor_layout not in ("HND", "NHD"):
+        raise GoalForceError(f"sageattn: tensor_layout {tensor_layout!r} (HND or NHD)")
+    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+        raise GoalForceError("sageattn: q, k, v must be 4-D")
+    if q.shape[-1] != 128 or k.shape[-1] != 128 or v.shape[-1] != 128:
+        raise GoalForceError(f"sageattn: head_dim {q.shape[-1]} is not supported (the kernel is built for 128)")
+    if tensor_layout == "HND":                                   # [B, n, s, d] -> [B, s, n, d]
+        q, k, v = (t.transpose(1, 2) for t in (q, k, v))
+    B, sq, n, _ = q.shape
+    if k.shape[0] != B or v.shape != k.shape or k.shape[2] != n:
+        raise GoalForceError("sageattn: q / k / v batch, head or key counts differ")
+    out = torch.empty((B, sq, n, 128), dtype=torch.bfloat16, device=q.device)
+    for b in range(B):
+        # [s, n, 128] -> [s, n*128]: a view when the token rows are contiguous (the reference's `b s (n d)` tensors are), else a copy
+        q2, k2, v2 = (t[b].reshape(t.shape[1], n * 128) for t in (q, k, v))
+        ops.sage_attn(q2, k2, v2, n, scale=sm_scale, out=out[b].view(sq, n * 128))
+    return out.transpose(1, 2) if tensor_layout == "HND" else out
+
+
 def pad_run(ctx2: torch.Tensor) -> int:
     """First row index n of the run of identical rows that ends the [L, D] tensor (rows n .. L-1 are all equal): L - 1 when the
     last two rows differ.  One comparison kernel and one 8-byte read-back per call.  The run is a property of the embedded context,
@@ -252,6 +293,11 @@ class SelfAttention(nn.Module):
         rows' log-sum-exp are stored under "attn" / "lse" so that the backward does not run the attention again; with
         keep["wide"] also the three projections ("qp", "kp" before their norm, "v")."""
         fp8 = getattr(self.q, "_gf_w8", None) is not None
+        sage = getattr(self, "_gf_sage", False)
+        if sage and keep is not None:
+            raise GoalForceError("training through a block with enable_sage_attention is refused (the sage backend has no backward): "
+                                 "call enable_sage_attention(module, False) first")
+        attn = ops.sage_attn if sage else ops.flash_attn
         xin = (x2 if isinstance(x2, QuantizedInput) else QuantizedInput(x2)) if fp8 else x2
         # Q leaves its RMSNorm + RoPE kernel already multiplied by c = softmax scale x log2(e) (the rotation table carries the factor:
         # RopeTable.scaled), and the attention is called with scale = ln 2, i.e. c = 1 inside — its `Q <- bf16(Q c)` is then exact.
@@ -274,7 +320,7 @@ class SelfAttention(nn.Module):
             q = linear(xin, self.q)
             ops.rmsnorm_rope(q, self.norm_q.weight, q_cos, q_sin, self.head_dim, self.norm_q.eps)
             hq = sp.heads_start(q, self.num_heads)
-            return sp.attention_started(hq, hk, hv, self.num_heads, tuple(q.shape), scale=attn_scale)
+            return sp.attention_started(hq, hk, hv, self.num_heads, tuple(q.shape), scale=attn_scale, backend="sage" if sage else "flash")
         q, k = linear(xin, self.q), linear(xin, self.k)
         if keep is not None and keep.get("wide"):      # training with room to spare: the pre-norm projections stay for the backward
             keep["qp"], keep["kp"] = q, k
@@ -285,23 +331,23 @@ class SelfAttention(nn.Module):
                 and ops.vt32_ok(x2.shape[0], self.num_heads, self.head_dim):
             # inference on one GPU: nothing but the attention reads V, so the projection writes it straight in the layout the
             # attention kernel wants (gf_linear_vt32: same bits as the plain projection + the transpose, one pass over V less)
-            return ops.flash_attn(q, k, None, self.num_heads, vt=ops.linear_vt32(x2, self.v.weight, self.v.bias), scale=attn_scale)
+            return attn(q, k, None, self.num_heads, vt=ops.linear_vt32(x2, self.v.weight, self.v.bias), scale=attn_scale)
         if sp is None and keep is None and fp8 and xin.is_cuda and self.v.weight.shape[0] >= 512 and self.v.weight.shape[1] % 128 == 0 \
                 and ops.vt32_ok(xin.shape[0], self.num_heads, self.head_dim):
             # config 5 on one GPU: the fp8 V projection writes the attention kernel's V^T operand as well (gf_linear_vt32_fp8)
             if self.v._gf_w8_key != param_key(self.v.weight):
                 self.v._gf_w8 = ops.cast_fp8(self.v.weight.detach().contiguous())
                 self.v._gf_w8_key = param_key(self.v.weight)
-            return ops.flash_attn(q, k, None, self.num_heads, vt=ops.linear_vt32_fp8(xin.x8, xin.scale, self.v._gf_w8, self.v.bias), scale=attn_scale)
+            return attn(q, k, None, self.num_heads, vt=ops.linear_vt32_fp8(xin.x8, xin.scale, self.v._gf_w8, self.v.bias), scale=attn_scale)
         v = linear(xin, self.v)
         if sp is not None:
-            return sp.attention(q, k, v, self.num_heads, scale=attn_scale)
+            return sp.attention(q, k, v, self.num_heads, scale=attn_scale, backend="sage" if sage else "flash")
         if keep is not None:
             keep["attn"], keep["lse"] = ops.flash_attn_lse(q, k, v, self.num_heads, scale=attn_scale)
             if keep.get("wide"):
                 keep["v"] = v
             return keep["attn"]
-        return ops.flash_attn(q, k, v, self.num_heads, scale=attn_scale)
+        return attn(q, k, v, self.num_heads, scale=attn_scale)
 
     def forward(self, x, freqs):
         x2 = _tokens2d(x)

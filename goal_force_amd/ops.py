@@ -388,6 +388,146 @@ def flash_attn(q, k, v, num_heads, out=None, scale=None, vt=None, last_key_mult=
     return out
 
 
+# ---- SageAttention backend (gf_sage_attention.hip; the recipe is stated in include/goalforce.h)
+SAGE_T, SAGE_TAU, SAGE_E = 128, 0, 8        # the kernel's key tile, lazy-rescale threshold and exponent offset
+SAGE_QBLK, SAGE_KBLK = 32, 64               # query rows per Q scale, keys per K scale
+_SAGE_WS = {}
+_SAGE_SCRATCH_PER_HEAD = 64 * 128 * 8
+
+
+def _sage_rows(t, name, num_heads):
+    """A [rows, >= heads*128] bf16 operand with contiguous rows (a column slice of a wider tensor is fine) -> (rows, row stride)."""
+    _req(t, name)
+    if t.dim() != 2 or t.stride(1) != 1:
+        raise GoalForceError(f"{name}: expected 2-D [len, heads*128] with contiguous rows")
+    if t.shape[1] != num_heads * 128:
+        raise GoalForceError(f"{name}: {t.shape[1]} columns for {num_heads} heads: the sage backend is built for head_dim 128")
+    if t.shape[0] < 1:
+        raise GoalForceError(f"{name}: empty sequence")
+    if t.stride(0) % 8 or t.data_ptr() % 16:
+        raise GoalForceError(f"{name}: row stride must be a multiple of 8 elements and the data 16-byte aligned")
+    return t.shape[0], t.stride(0)
+
+
+def _sage_scale(scale):
+    """The softmax scale: 1/sqrt(128) by default; positive and finite (the kernel takes the row maximum on the int32 dots)."""
+    scale = 1.0 / math.sqrt(128) if scale is None else float(scale)
+    if not (0.0 < scale < math.inf):
+        raise GoalForceError(f"sage attention: the softmax scale must be positive and finite, got {scale}")
+    return scale
+
+
+def _sage_scratch(num_heads, device):
+    return torch.empty((num_heads * _SAGE_SCRATCH_PER_HEAD,), dtype=torch.uint8, device=device)
+
+
+def sage_k_mean(k, num_heads):
+    """mu [heads, 128] fp32: the per-channel mean of k over its keys (gf_sage_k_mean; fp64 sums, one rounding)."""
+    skv, ldk = _sage_rows(k, "sage_k_mean.k", num_heads)
+    mu = torch.empty((num_heads, 128), dtype=torch.float32, device=k.device)
+    _lib.check(_lib.load().gf_sage_k_mean(_ptr(k), ldk, _ptr(mu), _ptr(_sage_scratch(num_heads, k.device)), skv, num_heads, _stream(k)),
+               "gf_sage_k_mean")
+    return mu
+
+
+def sage_quant_q(q, num_heads):
+    """(q8 [Sq, heads*128] int8, q_scale [heads, ceil(Sq/32)] fp32): one scale per (head, 32 rows) (gf_sage_quant_q)."""
+    sq, ldq = _sage_rows(q, "sage_quant_q.q", num_heads)
+    q8 = torch.empty((sq, num_heads * 128), dtype=torch.int8, device=q.device)
+    sc = torch.empty((num_heads, -(-sq // SAGE_QBLK)), dtype=torch.float32, device=q.device)
+    _lib.check(_lib.load().gf_sage_quant_q(_ptr(q), ldq, _ptr(q8), _ptr(sc), sq, num_heads, _stream(q)), "gf_sage_quant_q")
+    return q8, sc
+
+
+def sage_quant_k(k, num_heads, mu=None):
+    """(k8 [kv_pad8, heads*128] int8, k_scale [heads, kv_pad8/64] fp32, mu) of the smoothed k - mu (gf_sage_quant_k); kv_pad8 = keys
+    rounded up to 128, rows past the keys zero.  mu defaults to sage_k_mean(k)."""
+    skv, ldk = _sage_rows(k, "sage_quant_k.k", num_heads)
+    if mu is None:
+        mu = sage_k_mean(k, num_heads)
+    _req(mu, "sage_quant_k.mu", torch.float32)
+    if mu.numel() != num_heads * 128 or not mu.is_contiguous():
+        raise GoalForceError("sage_quant_k.mu: contiguous [heads, 128] fp32 expected")
+    kv_pad8 = -(-skv // SAGE_T) * SAGE_T
+    k8 = torch.empty((kv_pad8, num_heads * 128), dtype=torch.int8, device=k.device)
+    sc = torch.empty((num_heads, kv_pad8 // SAGE_KBLK), dtype=torch.float32, device=k.device)
+    _lib.check(_lib.load().gf_sage_quant_k(_ptr(k), ldk, _ptr(mu), _ptr(k8), _ptr(sc), skv, num_heads, _stream(k)), "gf_sage_quant_k")
+    return k8, sc, mu
+
+
+def sage_quant_vt(v, num_heads, vt=None, kv_len=None):
+    """(vt8 [heads*128, kv_pad8] e4m3 as uint8, v_scale [heads, 128] fp32) (gf_sage_quant_vt): V^T in the PV MFMA's key order, one
+    scale per channel.  From v [S, heads*128] bf16, or (v None) from the bf16 V^T `vt` that linear_vt32 / linear_vt32_fp8 wrote for
+    kv_len keys."""
+    if vt is None:
+        skv, ldv = _sage_rows(v, "sage_quant_vt.v", num_heads)
+        src, vt_in = v, 0
+    else:
+        _req(vt, "sage_quant_vt.vt")
+        if kv_len is None or kv_len < 1:
+            raise GoalForceError("sage_quant_vt: a V^T input needs kv_len")
+        skv, ldv, src, vt_in = kv_len, -(-kv_len // 64) * 64, vt, 1
+        if vt.numel() < num_heads * 128 * ldv:
+            raise GoalForceError("sage_quant_vt.vt: buffer smaller than heads*128*kv_pad")
+    kv_pad8 = -(-skv // SAGE_T) * SAGE_T
+    vt8 = torch.empty((num_heads * 128, kv_pad8), dtype=torch.uint8, device=src.device)
+    sc = torch.empty((num_heads, 128), dtype=torch.float32, device=src.device)
+    _lib.check(_lib.load().gf_sage_quant_vt(_ptr(src), ldv, vt_in, _ptr(vt8), _ptr(sc), _ptr(_sage_scratch(num_heads, src.device)), skv,
+                                            num_heads, _stream(src)), "gf_sage_quant_vt")
+    return vt8, sc
+
+
+def sage_attn_quantized(q8, q_scale, k8, k_scale, vt8, v_scale, kv_len, num_heads, scale=None, out=None):
+    """The attention kernel alone (gf_sage_attn_fwd) on the operands of sage_quant_q / _k / _vt."""
+    sq = q8.shape[0]
+    scale = _sage_scale(scale)
+    if out is None:
+        out = torch.empty((sq, num_heads * 128), dtype=_BF16, device=q8.device)
+    _lib.check(_lib.load().gf_sage_attn_fwd(_ptr(q8), _ptr(q_scale), _ptr(k8), _ptr(k_scale), _ptr(vt8), _ptr(v_scale), _ptr(out),
+                                            out.stride(0), sq, kv_len, num_heads, scale, _stream(q8)), "gf_sage_attn_fwd")
+    return out
+
+
+def sage_attn(q, k, v, num_heads, scale=None, vt=None, out=None):
+    """SageAttention-style softmax(q k^T * scale) v per head (gf_sage_attn: K smoothing, int8 QK^T, e4m3 PV, fp32 accumulation);
+    q [Sq, H*128], k / v [Skv, H*128] bf16 with contiguous rows (column slices OK).  `vt` (instead of v): the bf16 V^T that
+    linear_vt32 / linear_vt32_fp8 wrote for these keys.  scale defaults to 1/sqrt(128).  Workspace: one reusable buffer per
+    (device, stream), as the V^T workspace."""
+    scale = _sage_scale(scale)
+    sq, ldq = _sage_rows(q, "sage_attn.q", num_heads)
+    skv, ldk = _sage_rows(k, "sage_attn.k", num_heads)
+    if vt is None:
+        sv, ldv = _sage_rows(v, "sage_attn.v", num_heads)
+        if sv != skv:
+            raise GoalForceError(f"sage_attn: k has {skv} keys, v {sv}")
+        src, vt_in = v, 0
+    else:
+        _req(vt, "sage_attn.vt")
+        ldv, src, vt_in = -(-skv // 64) * 64, vt, 1
+        if vt.numel() < num_heads * 128 * ldv:
+            raise GoalForceError("sage_attn.vt: buffer smaller than heads*128*kv_pad")
+    if out is None:
+        out = torch.empty((sq, num_heads * 128), dtype=_BF16, device=q.device)
+    elif out.dtype != _BF16 or out.dim() != 2 or out.stride(1) != 1 or tuple(out.shape) != (sq, num_heads * 128) or out.stride(0) % 8:
+        raise GoalForceError(f"sage_attn.out: bf16 [{sq}, {num_heads * 128}] with contiguous rows expected")
+    lib = _lib.load()
+    nbytes = int(lib.gf_sage_workspace_bytes(sq, skv, num_heads))
+    key = (q.device.index, torch.cuda.current_stream(q.device).cuda_stream)
+    ws = _SAGE_WS.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = _SAGE_WS[key] = torch.empty((nbytes,), dtype=torch.uint8, device=q.device)
+    prof = PROFILE_ATTN
+    if prof is not None:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+    _lib.check(lib.gf_sage_attn(_ptr(q), ldq, _ptr(k), ldk, _ptr(src), ldv, vt_in, _ptr(out), out.stride(0), sq, skv, num_heads, scale,
+                                _ptr(ws), _stream(q)), "gf_sage_attn")
+    if prof is not None:
+        e1.record()
+        prof.append((e0, e1, sq, skv, num_heads))
+    return out
+
+
 CROSS_FOLD_MAX_KEYS = 63   # gf_cross_probs holds a row's keys and the last key's residue column in one 64-key tile
 
 

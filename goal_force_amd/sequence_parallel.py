@@ -42,6 +42,12 @@ from . import ops
 from ._lib import GoalForceError
 
 
+def _backend(name: str):
+    if name not in ("flash", "sage"):
+        raise GoalForceError(f"sequence parallel: unknown attention backend {name!r} (flash or sage)")
+    return ops.sage_attn if name == "sage" else ops.flash_attn
+
+
 class SequenceParallel:
     """One sequence-parallel group: `group` is a torch.distributed group of P ranks (None = the world group)."""
 
@@ -116,9 +122,11 @@ class SequenceParallel:
         work = dist.all_to_all_single(recv, send, group=self.group, async_op=True)
         return work, recv, send                                # (send is kept alive until the wait)
 
-    def attention_started(self, hq, hk, hv, num_heads: int, out_shape, scale=None) -> torch.Tensor:
+    def attention_started(self, hq, hk, hv, num_heads: int, out_shape, scale=None, backend="flash") -> torch.Tensor:
         """The attention over this rank's head group from three started exchanges (heads_start), and the heads-for-tokens exchange
-        back.  The head group is computed in two halves: the first half's way back flies under the second half's attention."""
+        back.  The head group is computed in two halves: the first half's way back flies under the second half's attention.
+        backend: "flash" (ops.flash_attn) or "sage" (ops.sage_attn, dit.enable_sage_attention)."""
+        attn = _backend(backend)
         p = self.size
         if num_heads % p:
             raise GoalForceError(f"sequence parallel: {num_heads} heads do not divide by {p} ranks")
@@ -132,7 +140,7 @@ class SequenceParallel:
         backs = []
         for h0, h1 in parts:
             c0, c1 = h0 * hd, h1 * hd
-            o = ops.flash_attn(q[:, c0:c1], k[:, c0:c1], v[:, c0:c1], h1 - h0, scale=scale)   # [S, (h1 - h0) * hd]
+            o = attn(q[:, c0:c1], k[:, c0:c1], v[:, c0:c1], h1 - h0, scale=scale)   # [S, (h1 - h0) * hd]
             back = torch.empty((p, sl, c1 - c0), dtype=o.dtype, device=o.device)
             backs.append((dist.all_to_all_single(back, o.reshape(p, sl, c1 - c0), group=self.group, async_op=True), back, o, c0, c1))
         out = torch.empty((sl, d), dtype=q.dtype, device=q.device)
@@ -142,14 +150,14 @@ class SequenceParallel:
             ov[:, :, c0:c1].copy_(back.transpose(0, 1))
         return out
 
-    def attention(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_heads: int, scale=None) -> torch.Tensor:
+    def attention(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_heads: int, scale=None, backend="flash") -> torch.Tensor:
         """q, k, v: this rank's tokens [S/P, NH*DH] (already normed and rotated) -> attention output [S/P, NH*DH]."""
         if self.size == 1:
-            return ops.flash_attn(q, k, v, num_heads, scale=scale)
+            return _backend(backend)(q, k, v, num_heads, scale=scale)
         if num_heads % self.size:
             raise GoalForceError(f"sequence parallel: {num_heads} heads do not divide by {self.size} ranks")
         hk, hv, hq = self.heads_start(k, num_heads), self.heads_start(v, num_heads), self.heads_start(q, num_heads)
-        return self.attention_started(hq, hk, hv, num_heads, tuple(q.shape), scale=scale)
+        return self.attention_started(hq, hk, hv, num_heads, tuple(q.shape), scale=scale, backend=backend)
 
     def preflight(self, device) -> int:
         """One head all-to-all at production size (S = 32760 tokens, D = 5120: [S/P, D] bf16 per rank) with a content check;

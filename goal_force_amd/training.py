@@ -255,6 +255,9 @@ class DiTBlockFn(torch.autograd.Function):
         if any(getattr(m, "_gf_w8", None) is not None for m in block.modules()):
             # the backward recomputes the block on the bf16 kernels: an fp8 forward would not be the function differentiated
             raise GoalForceError("training through an enable_fp8 block is refused: call enable_fp8(module, False) first")
+        if getattr(block.self_attn, "_gf_sage", False):
+            # no backward exists for the sage backend (nor in the sageattention package): the backward would differentiate another function
+            raise GoalForceError("training through a block with enable_sage_attention is refused: call enable_sage_attention(module, False) first")
         ctx.param_needs = [p.requires_grad for p in params]
         ctx.q_prescale = bool(ops._OPT["attn_q_prescale"])       # what the forward's self-attention saw is what the backward rebuilds (dit.SelfAttention.attend)
         keep = ({"wide": True} if _wide_fits(x2) else {}) if KEEP_ATTENTION else None

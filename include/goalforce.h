@@ -488,6 +488,40 @@ GF_API int gf_vae_rmsnorm_silu_padded(const void* x, const void* gamma, void* ou
                                       int silu, void* stream);
 GF_API int gf_vae_upsample2x_padded(const void* x, void* out_interior, int64_t T, int64_t H, int64_t W, int64_t C, void* stream);
 
+/* ------------------------------------------------------------------------
+ * SageAttention backend (the reference's `sageattn(q, k, v)` branch of flash_attention, DIT:22-26, 50-54): int8 QK^T with
+ * smoothed K, e4m3 P·V, fp32 accumulation; head_dim 128, non-causal, no mask.  The recipe (granularities are this project's own):
+ *   mu[h][c]     = fp32 mean of k over the kv_len keys (fp64 sums);  k~ = fp32(k) - mu
+ *   q8, q_scale  : int8 codes, one scale per (head, 32 query rows from row 0): scale = amax / 127, code = rne(x * (127 / amax))
+ *                  clamped to +-127; an all-zero block has scale 0 and codes 0.  k8, k_scale: the same on k~ per (head, 64 keys)
+ *   vt8, v_scale : e4m3fn codes of V^T, one scale per (head, channel) over all keys: scale = amax / 448, code = e4m3(v * (448 / amax))
+ *   s            = float(int32 dot) * fp32(fp32(s_q s_k) * c), c = scale * log2(e)
+ *   per 128-key tile in key order: m = running row maximum of s, P = e4m3(exp2(s - m + 8)), l = sum of that P, acc = sum P V_code
+ *   (fp32, rescaled by exp2(m_old - m_new) when m moves); O = bf16(acc / l * v_scale)
+ * Layouts (caller-owned; the library never allocates):
+ *   q8 [q_len][heads*128] int8;  q_scale [heads][ceil(q_len / 32)] fp32
+ *   k8 [kv_pad8][heads*128] int8 (kv_pad8 = kv_len rounded up to 128, rows >= kv_len zero);  k_scale [heads][kv_pad8 / 64] fp32
+ *   vt8 [heads*128][kv_pad8] e4m3, inside every 128-key slice key k at position 32 ((k >> 2) & 3) + 4 (k >> 4) + (k & 3) (the PV
+ *       MFMA operand order), keys >= kv_len zero;  v_scale [heads][128] fp32;  mu [heads][128] fp32
+ *   scratch: heads * 64 * 128 * 8 bytes (row-chunk partial sums of gf_sage_k_mean / maxima of gf_sage_quant_vt)
+ * Inputs are bf16 with a row stride (a column slice of a wider tensor is fine), 16-byte aligned, strides multiples of 8. */
+GF_API int64_t gf_sage_workspace_bytes(int64_t q_len, int64_t kv_len, int64_t heads);   /* bytes gf_sage_attn needs */
+GF_API int gf_sage_k_mean(const void* k, int64_t ldk, float* mu, void* scratch, int64_t kv_len, int64_t heads, void* stream);
+GF_API int gf_sage_quant_q(const void* q, int64_t ldq, void* q8, float* q_scale, int64_t q_len, int64_t heads, void* stream);
+GF_API int gf_sage_quant_k(const void* k, int64_t ldk, const float* mu, void* k8, float* k_scale, int64_t kv_len, int64_t heads,
+                           void* stream);
+/* vt_in = 0: v is V [kv_len][ldv];  vt_in = 1: v is the bf16 V^T of gf_linear_vt32 / gf_linear_vt32_fp8 / gf_transpose_v32 with
+ * ldv = its kv_pad (a multiple of 64). */
+GF_API int gf_sage_quant_vt(const void* v, int64_t ldv, int vt_in, void* vt8, float* v_scale, void* scratch, int64_t kv_len,
+                            int64_t heads, void* stream);
+GF_API int gf_sage_attn_fwd(const void* q8, const float* q_scale, const void* k8, const float* k_scale, const void* vt8,
+                            const float* v_scale, void* o, int64_t ldo, int64_t q_len, int64_t kv_len, int64_t heads, float scale,
+                            void* stream);
+/* gf_sage_attn — the four quantisation passes and the attention in one call; ws = gf_sage_workspace_bytes bytes, laid out as
+ * q8, k8, vt8, q_scale, k_scale, v_scale, mu, scratch, each starting on a 256-byte boundary. */
+GF_API int gf_sage_attn(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, int vt_in, void* o,
+                        int64_t ldo, int64_t q_len, int64_t kv_len, int64_t heads, float scale, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,8 @@ BIN = os.path.join(ROOT, "build", "issue_probe")
 # one slot = one MFMA (or none) + extras; 8 slots per loop trip, accumulators rotate over a[0:63]
 MIXES = [
     ("mfma", dict(m=1)),
+    ("mfma_i8_16x16x64", dict(mi8=1)),
+    ("mfma_f8f6f4_16x16x128", dict(mf8=1)),
     ("mfma+1exp", dict(m=1, exp=1)),
     ("mfma+2exp", dict(m=1, exp=2)),
     ("mfma+4exp", dict(m=1, exp=4)),
@@ -80,6 +82,12 @@ def body(mix):
         if mix.get("m16"):
             a4 = 4 * (s % 8)
             lines.append(f"v_mfma_f32_16x16x32_bf16 a[{a4}:{a4+3}], v[8:11], v[12:15], a[{a4}:{a4+3}]")
+        if mix.get("mi8"):       # the SageAttention QK^T MFMA (2 x the bf16 16x16x32 K per instruction)
+            a4 = 4 * (s % 8)
+            lines.append(f"v_mfma_i32_16x16x64_i8 a[{a4}:{a4+3}], v[8:11], v[12:15], a[{a4}:{a4+3}]")
+        if mix.get("mf8"):       # the SageAttention PV MFMA: K = 128 f8f6f4, e4m3 x e4m3
+            a4 = 4 * (s % 8)
+            lines.append(f"v_mfma_f32_16x16x128_f8f6f4 a[{a4}:{a4+3}], v[84:91], v[92:99], a[{a4}:{a4+3}]")
         for k in range(mix.get("lds", 0)):
             r = 52 + 2 * ((2 * s + k) % 16)
             lines.append(f"ds_read_b64_tr_b16 v[{r}:{r+1}], v16 offset:{4096 * ((2 * s + k) % 4)}")
