@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import re
 import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -14,28 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libgoalforce_hip.so")
 # GOALFORCE_HIP_LIB: A/B a differently built libgoalforce_hip.so (kernel tuning); it is still the HIP library, never a fallback
 LIB_PATH = os.environ.get("GOALFORCE_HIP_LIB", LIB_PATH)
 
-# every symbol include/goalforce.h declares (tests check the .so exports exactly these)
-SYMBOLS = (
-    "gf_version", "gf_last_error", "gf_abi_version", "gf_set_option", "gf_get_option", "gf_reset_options",
-    "gf_modulation", "gf_layernorm_modulate", "gf_rmsnorm_rope", "gf_gemm_bf16", "gf_flash_attn_fwd",
-    "gf_patchify_im2col", "gf_unpatchify", "gf_cfg_euler_step", "gf_act", "gf_add_bf16",
-    "gf_force_map",
-    "gf_vae_prep_latent", "gf_vae_im2col", "gf_vae_finish_latent", "gf_vae_rmsnorm_silu", "gf_softmax_rows", "gf_rowmax_neg_bf16", "gf_transpose_pad",
-    "gf_vae_tile_blend", "gf_vae_tile_finalize",
-    "gf_quant_fp8_rowscale", "gf_cast_fp8", "gf_gemm_fp8", "gf_layernorm_modulate_fp8", "gf_modulate", "gf_gate_residual", "gf_rope_apply", "gf_linear_vt32_fp8",
-    "gf_flash_attn_fwd_lse", "gf_flash_attn_bwd", "gf_flash_attn_bwd_workspace_bytes",
-    "gf_layernorm_bwd", "gf_rmsnorm_rope_bwd", "gf_colsum", "gf_act_bwd", "gf_mse_loss", "gf_adamw_step", "gf_f32_to_bf16", "gf_sumsq",
-    "gf_transpose_v", "gf_flash_attn_fwd_vt", "gf_transpose_v32", "gf_flash_attn_fwd_vt32", "gf_linear_vt32",
-    "gf_conv3d_bf16", "gf_conv3d_padded_bf16", "gf_vae_rmsnorm_silu_padded", "gf_vae_upsample2x_padded", "gf_gemm_bf16_batched", "gf_transpose_pad_batched",
-    "gf_resize_lanczos4_u8", "gf_resize_area_u8", "gf_canny_u8", "gf_flash_attn_fwd_lastmult",
-    "gf_cross_probs", "gf_cross_fold_table",
-    "gf_sage_workspace_bytes", "gf_sage_k_mean", "gf_sage_quant_q", "gf_sage_quant_k", "gf_sage_quant_vt", "gf_sage_attn_fwd", "gf_sage_attn",
-)
-
-# the C ABI revision these bindings were written against (csrc/gf_abi.hip: GF_ABI_VERSION).  A stale or foreign .so whose entry
-# points take differently sized buffers (gf_flash_attn_bwd's workspace grew 3x between revisions 7 and 10 under an unchanged
-# signature) is refused at load time instead of overrunning memory.
-ABI_VERSION = 20
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "goalforce.h")
 
 EPI_BIAS, EPI_BIAS_GELU_TANH, EPI_BIAS_GATE_RESID, EPI_BIAS_RESID, EPI_BIAS_SILU, EPI_BIAS_MUL = range(6)
 
@@ -44,96 +24,81 @@ class GoalForceError(RuntimeError):
     """Raised when the HIP library is missing or a gf_* call returns an error."""
 
 
+# ---- the binding is READ from include/goalforce.h, the file the compiler checks every definition against: the symbol list, each
+# entry point's restype / argtypes and the ABI revision have no second copy here.  A new entry point is declared there, defined
+# in csrc, GF_ABI_VERSION is bumped, and ops.py gets its wrapper.  The parser fails closed: a type outside _CTYPES or a GF_API
+# line it cannot take apart raises GoalForceError at import — ctypes would accept a wrong row and hand a kernel a shifted pointer.
+_CTYPES = {"void": None, "int": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "uint32_t": ctypes.c_uint32}
+_DECL = re.compile(r"\s+([\w\s*]+?)\s*\b(gf_\w+)\s*\(([^()]*)\)\s*;")
+
+
+def _ctype(text, decl):
+    """The ctypes type of one C type as the header spells it: the scalars of _CTYPES, `const char*` -> c_char_p, any other
+    one-level pointer -> c_void_p (which takes None, an integer address and ctypes.byref(...))."""
+    words = text.replace("*", " * ").split()
+    if words == ["const", "char", "*"]:
+        return ctypes.c_char_p
+    if words[:1] == ["const"]:
+        words = words[1:]
+    if len(words) == 2 and words[1] == "*" and words[0].isidentifier():
+        return ctypes.c_void_p
+    if len(words) != 1 or words[0] not in _CTYPES:
+        raise GoalForceError(f"goalforce.h: type {text.strip()!r} in `{decl}` is outside the binding's type map")
+    return _CTYPES[words[0]]
+
+
+def parse_header(text):
+    """{name: (restype, [argtypes])} of every `GF_API <ret> gf_name(<params>);` in the text of a goalforce.h, in its order."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)          # the preprocessor lines (GF_API's own #define among them)
+    out = {}
+    for chunk in re.split(r"\bGF_API\b", text)[1:]:
+        m = _DECL.match(chunk)
+        if m is None:
+            raise GoalForceError(f"goalforce.h: cannot take apart the declaration `GF_API{' '.join(chunk.split())[:100]}`")
+        ret, name, params = m.groups()
+        decl = " ".join(m.group(0).split())
+        if name in out:
+            raise GoalForceError(f"goalforce.h: {name} is declared twice")
+        argtypes = []
+        if params.strip() != "void":
+            for p in params.split(","):
+                pm = re.fullmatch(r"\s*(.*?[\s*])(\w+)\s*", p, flags=re.S)     # <type> <parameter name>
+                if pm is None:
+                    raise GoalForceError(f"goalforce.h: parameter {p.strip()!r} of `{decl}` is not `<type> <name>`")
+                argtypes.append(_ctype(pm.group(1), decl))
+                if argtypes[-1] is None:
+                    raise GoalForceError(f"goalforce.h: a void parameter in `{decl}`")
+        out[name] = (_ctype(ret, decl), argtypes)
+    return out
+
+
+def _read_header():
+    try:
+        with open(HEADER_PATH, encoding="utf-8") as f:
+            text = f.read()
+    except OSError as e:
+        raise GoalForceError(f"{HEADER_PATH}: the C ABI's header, which these bindings are read from, cannot be read ({e})") from e
+    rev = re.findall(r"^#define GF_ABI_VERSION (\d+)\s*$", text, flags=re.M)
+    if len(rev) != 1:
+        raise GoalForceError(f"{HEADER_PATH}: expected exactly one `#define GF_ABI_VERSION <n>`, found {len(rev)}")
+    return parse_header(text), int(rev[0])
+
+
+# BINDINGS: every entry point the header declares; ABI_VERSION: the C ABI revision it states (gf_abi_version() of a library built
+# from it).  A stale or foreign .so whose entry points take differently sized buffers (gf_flash_attn_bwd's workspace grew 3x
+# between revisions 7 and 10 under an unchanged signature) is refused at load time instead of overrunning memory.
+BINDINGS, ABI_VERSION = _read_header()
+SYMBOLS = tuple(BINDINGS)       # tests check the .so exports exactly these
+
 _lib = None
 _lock = threading.Lock()
 
-_vp, _i64, _f32, _int = ctypes.c_void_p, ctypes.c_int64, ctypes.c_float, ctypes.c_int
-
 
 def _declare(lib):
-    lib.gf_version.restype = ctypes.c_char_p
-    lib.gf_version.argtypes = []
-    lib.gf_last_error.restype = ctypes.c_char_p
-    lib.gf_last_error.argtypes = []
-    lib.gf_abi_version.restype = _int
-    lib.gf_abi_version.argtypes = []
-    lib.gf_set_option.restype = _int
-    lib.gf_set_option.argtypes = [ctypes.c_char_p, _int]
-    lib.gf_get_option.restype = _int
-    lib.gf_get_option.argtypes = [ctypes.c_char_p, ctypes.POINTER(_int)]
-    lib.gf_reset_options.restype = None
-    lib.gf_reset_options.argtypes = []
-    sigs = {
-        "gf_layernorm_modulate": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32, _vp],
-        "gf_modulation": [_vp, _vp, _vp, _i64, _i64, _i64, ctypes.c_uint32, _vp],
-        "gf_rmsnorm_rope": [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32, _vp],
-        "gf_gemm_bf16": [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _int, _vp, _i64, _vp, _vp],
-        "gf_flash_attn_fwd": [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _vp],
-        "gf_flash_attn_fwd_lastmult": [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _vp],
-        "gf_cross_probs": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _vp],
-        "gf_cross_fold_table": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _vp],
-        "gf_flash_attn_fwd_lse": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _vp],
-        "gf_flash_attn_bwd": [_vp] * 10 + [_i64] * 12 + [_f32, _vp],
-        "gf_flash_attn_bwd_workspace_bytes": [_i64] * 3,
-        "gf_layernorm_bwd": [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _f32, _vp],
-        "gf_rmsnorm_rope_bwd": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _f32, _vp],
-        "gf_colsum": [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _vp],
-        "gf_act_bwd": [_vp, _vp, _vp, _i64, _int, _vp],
-        "gf_mse_loss": [_vp, _vp, _vp, _vp, _i64, _f32, _vp],
-        "gf_adamw_step": [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _i64, _f32, _vp],
-        "gf_f32_to_bf16": [_vp, _vp, _i64, _vp],
-        "gf_sumsq": [_vp, _i64, _vp, _vp],
-        "gf_transpose_v": [_vp, _i64, _vp, _i64, _i64, _i64, _vp],
-        "gf_flash_attn_fwd_vt": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _vp],
-        "gf_transpose_v32": [_vp, _i64, _vp, _i64, _i64, _i64, _vp],
-        "gf_linear_vt32": [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _vp],
-        "gf_flash_attn_fwd_vt32": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _vp],
-        "gf_patchify_im2col": [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp],
-        "gf_unpatchify": [_vp, _vp, _i64, _i64, _i64, _i64, _vp],
-        "gf_cfg_euler_step": [_vp, _vp, _vp, _f32, _f32, _i64, _vp],
-        "gf_act": [_vp, _vp, _i64, _int, _vp],
-        "gf_add_bf16": [_vp, _vp, _vp, _i64, _vp],
-        "gf_vae_prep_latent": [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp],
-        "gf_vae_im2col": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _int, _i64, _i64, _i64, _vp],
-        "gf_conv3d_bf16": [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _int,
-                           _i64, _i64, _int, _vp, _i64, _vp],
-        "gf_vae_finish_latent": [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp],
-        "gf_vae_rmsnorm_silu": [_vp, _vp, _vp, _i64, _i64, _int, _vp],
-        "gf_vae_rmsnorm_silu_padded": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _vp],
-        "gf_conv3d_padded_bf16": [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _vp, _i64, _vp],
-        "gf_vae_upsample2x_padded": [_vp, _vp, _i64, _i64, _i64, _i64, _vp],
-        "gf_softmax_rows": [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _f32, _vp],
-        "gf_rowmax_neg_bf16": [_vp, _i64, _vp, _i64, _i64, _i64, _vp],
-        "gf_transpose_pad": [_vp, _i64, _vp, _i64, _i64, _i64, _vp],
-        "gf_transpose_pad_batched": [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp],
-        "gf_gemm_bf16_batched": [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp],
-        "gf_vae_tile_blend": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _int,
-                              _i64, _i64, _vp],
-        "gf_vae_tile_finalize": [_vp, _vp, _i64, _i64, _int, _vp],
-        "gf_quant_fp8_rowscale": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp],
-        "gf_modulate": [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp],
-        "gf_gate_residual": [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp],
-        "gf_linear_vt32_fp8": [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _vp],
-        "gf_rope_apply": [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp],
-        "gf_layernorm_modulate_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32, _vp],
-        "gf_cast_fp8": [_vp, _vp, _i64, _vp],
-        "gf_gemm_fp8": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _vp, _i64, _vp, _vp],
-        "gf_force_map": [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _int, _vp],
-        "gf_resize_lanczos4_u8": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp],
-        "gf_resize_area_u8": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _int, _vp],
-        "gf_canny_u8": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _int, _int, _int, _vp],
-        "gf_sage_workspace_bytes": [_i64] * 3,
-        "gf_sage_k_mean": [_vp, _i64, _vp, _vp, _i64, _i64, _vp],
-        "gf_sage_quant_q": [_vp, _i64, _vp, _vp, _i64, _i64, _vp],
-        "gf_sage_quant_k": [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp],
-        "gf_sage_quant_vt": [_vp, _i64, _int, _vp, _vp, _vp, _i64, _i64, _vp],
-        "gf_sage_attn_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32, _vp],
-        "gf_sage_attn": [_vp, _i64, _vp, _i64, _vp, _i64, _int, _vp, _i64, _i64, _i64, _i64, _f32, _vp, _vp],
-    }
-    for name, argtypes in sigs.items():
+    for name, (restype, argtypes) in BINDINGS.items():
         fn = getattr(lib, name)
-        fn.restype = _i64 if name.endswith("_bytes") else _int
-        fn.argtypes = argtypes
+        fn.restype, fn.argtypes = restype, argtypes
 
 
 def load():
@@ -158,7 +123,7 @@ def load():
             # must reach the user instead of a bare AttributeError out of _declare
             rebuild = "rebuild the library (`make -C goal_force_amd/csrc`)"
             try:
-                lib.gf_abi_version.restype = _int
+                lib.gf_abi_version.restype = ctypes.c_int
                 have = int(lib.gf_abi_version())
             except AttributeError as e:
                 raise GoalForceError(f"{LIB_PATH} predates the C ABI revision export: {rebuild}") from e

@@ -5,8 +5,6 @@
 #include <cstdlib>
 #include <cstring>
 
-#define GF_ABI_VERSION 20
-
 static thread_local char g_err[512] = "";
 
 void gf_set_error(const char* fmt, ...) {

@@ -21,6 +21,7 @@ __all__ = [
 ]
 
 _BF16 = torch.bfloat16
+_FP8 = torch.float8_e4m3fn
 
 # Optional per-launch timing of the dominant kernel (bench.py's roofline leg): when PROFILE_ATTN is a list,
 # flash_attn() brackets every launch with events recorded on the launch stream and appends
@@ -65,6 +66,95 @@ def _rows2d(t: torch.Tensor, name: str):
     return v, v.shape[0], v.shape[1], v.stride(0)
 
 
+def _vec(t, name: str, n: int, dtype=_BF16, required=False):
+    """A vector operand (bias, gate, scale ...): `dtype`, n elements, contiguous; None passes unless `required`."""
+    if t is None:
+        if required:
+            raise GoalForceError(f"{name}: required")
+        return
+    _req(t, name, dtype)
+    if t.numel() != n or not t.is_contiguous():
+        raise GoalForceError(f"{name}: expected contiguous [{n}]")
+
+
+def _mat(t: torch.Tensor, name: str, dtype=_BF16):
+    """A 2-D operand with contiguous rows (a column slice of a wider tensor is fine; the row stride goes to the kernel)."""
+    _req(t, name, dtype)
+    if t.dim() != 2 or t.stride(1) != 1:
+        raise GoalForceError(f"{name}: expected 2-D with contiguous rows, got {tuple(t.shape)}")
+
+
+def _weight(w: torch.Tensor, name: str, K: int, dtype=_BF16):
+    """A weight matrix [N, K] with contiguous rows -> (N, row stride)."""
+    _mat(w, name, dtype)
+    if w.shape[1] != K:
+        raise GoalForceError(f"{name}: expected [N, {K}] with contiguous rows, got {tuple(w.shape)}")
+    return w.shape[0], w.stride(0)
+
+
+def _out(out, name: str, rows: int, cols: int, device):
+    """The [rows, cols] bf16 result: a new tensor, or the caller's `out` (that shape, contiguous rows)."""
+    if out is None:
+        return torch.empty((rows, cols), dtype=_BF16, device=device)
+    _mat(out, name)
+    if tuple(out.shape) != (rows, cols):
+        raise GoalForceError(f"{name}: expected [{rows}, {cols}], got {tuple(out.shape)}")
+    return out
+
+
+def _flat(op: str, **tensors):
+    """The operands of an elementwise kernel: bf16, contiguous, all of one size (None: an optional one left out) -> that size."""
+    n = next(iter(tensors.values())).numel()
+    for name, t in tensors.items():
+        if t is None:
+            continue
+        _req(t, f"{op}.{name}")
+        if not t.is_contiguous() or t.numel() != n:
+            raise GoalForceError(f"{op}: {' / '.join(tensors)} must be contiguous and equal-sized")
+    return n
+
+
+def kv_pad(skv: int) -> int:
+    """The key length rounded up to the 64-key tile: the row length of the V^T operand."""
+    return -(-skv // 64) * 64
+
+
+class _timed:
+    """`with _timed(PROFILE_X, *what):` around a launch: when the list is set (read by the caller, per call), events recorded on
+    the launch stream bracket it and (start, end, *what) is appended; None: nothing.  A launch that raised appends nothing."""
+    __slots__ = ("prof", "what", "e0")
+
+    def __init__(self, prof, *what):
+        self.prof, self.what = prof, what
+
+    def __enter__(self):
+        if self.prof is not None:
+            self.e0 = torch.cuda.Event(enable_timing=True)
+            self.e0.record()
+
+    def __exit__(self, exc_type, *exc):
+        if self.prof is not None and exc_type is None:
+            e1 = torch.cuda.Event(enable_timing=True)
+            e1.record()
+            self.prof.append((self.e0, e1) + self.what)
+        return False
+
+
+def _linear_operands(a, w, scale):
+    """The operands of a linear layer -> (a as [M, K] rows, M, K, lda, N, ldw): a [.., K] and w [N, K] bf16, or (`scale` given:
+    the fp8_linear contract) a [M, K] and w [N, K] float8_e4m3fn with one fp32 scale per row of a."""
+    if scale is None:
+        _req(a, "linear: activation")
+        av, M, K, lda = _rows2d(a, "linear: activation")
+        N, ldw = _weight(w, "linear: weight", K)
+    else:
+        _mat(a, "fp8 linear: activation", _FP8)
+        av, (M, K), lda = a, a.shape, a.stride(0)
+        N, ldw = _weight(w, "fp8 linear: weight", K, _FP8)
+        _vec(scale, "fp8 linear: row scale", M, torch.float32)
+    return av, M, K, lda, N, ldw
+
+
 def modulation(param, t, onep_mask: int):
     """out[i] = bf16(param[i] + t[i % t_rows]); rows in onep_mask get bf16(1 + .) — gf_modulation.
     param [.., k, dim], t [.., t_rows, dim] -> out [k, dim]."""
@@ -88,11 +178,10 @@ def layernorm_modulate(x, weight=None, bias=None, scale1p=None, shift=None, eps=
     if out is None:
         out = torch.empty(x.shape, dtype=_BF16, device=x.device)
     ov, _, _, os_ = _rows2d(out, "layernorm_modulate.out")
-    for n, t in (("weight", weight), ("bias", bias), ("scale1p", scale1p), ("shift", shift)):
-        if t is not None:
-            _req(t, f"layernorm_modulate.{n}")
-            if t.numel() != dim or not t.is_contiguous():
-                raise GoalForceError(f"layernorm_modulate.{n}: expected contiguous [{dim}]")
+    _vec(weight, "layernorm_modulate.weight", dim)
+    _vec(bias, "layernorm_modulate.bias", dim)
+    _vec(scale1p, "layernorm_modulate.scale1p", dim)
+    _vec(shift, "layernorm_modulate.shift", dim)
     _lib.check(_lib.load().gf_layernorm_modulate(_ptr(xv), _ptr(ov), _ptr(weight), _ptr(bias), _ptr(scale1p),
                                                  _ptr(shift), rows, dim, xs, os_, float(eps), _stream(x)),
                "gf_layernorm_modulate")
@@ -119,10 +208,8 @@ def modulate(x, shift, scale):
     """x * (1 + scale) + shift in the reference's eager bf16 rounding sequence (DIT:64-65) — gf_modulate; shift / scale [dim]."""
     _req(x, "modulate.x")
     xv, rows, dim, xs = _rows2d(x, "modulate.x")
-    for n, t in (("shift", shift), ("scale", scale)):
-        _req(t, f"modulate.{n}")
-        if t.numel() != dim or not t.is_contiguous():
-            raise GoalForceError(f"modulate.{n}: expected contiguous [{dim}] (batch 1)")
+    _vec(shift, "modulate.shift", dim, required=True)
+    _vec(scale, "modulate.scale", dim, required=True)
     out = torch.empty(x.shape, dtype=_BF16, device=x.device)
     ov, _, _, os_ = _rows2d(out, "modulate.out")
     _lib.check(_lib.load().gf_modulate(_ptr(xv), _ptr(ov), _ptr(scale), _ptr(shift), rows, dim, xs, os_, _stream(x)), "gf_modulate")
@@ -133,11 +220,11 @@ def gate_residual(x, gate, residual):
     """x + gate * residual in the reference's eager bf16 rounding order (DIT:189-194) — gf_gate_residual; gate [dim]."""
     _req(x, "gate_residual.x")
     _req(residual, "gate_residual.residual")
-    _req(gate, "gate_residual.gate")
     xv, rows, dim, xs = _rows2d(x, "gate_residual.x")
     rv, rrows, rdim, rs = _rows2d(residual, "gate_residual.residual")
-    if (rrows, rdim) != (rows, dim) or gate.numel() != dim or not gate.is_contiguous():
-        raise GoalForceError(f"gate_residual: residual must match x [{rows}, {dim}] and gate be contiguous [{dim}] (batch 1)")
+    if (rrows, rdim) != (rows, dim):
+        raise GoalForceError(f"gate_residual: residual must match x [{rows}, {dim}]")
+    _vec(gate, "gate_residual.gate", dim, required=True)
     out = torch.empty(x.shape, dtype=_BF16, device=x.device)
     ov, _, _, os_ = _rows2d(out, "gate_residual.out")
     _lib.check(_lib.load().gf_gate_residual(_ptr(xv), _ptr(gate), _ptr(rv), _ptr(ov), rows, dim, xs, rs, os_, _stream(x)),
@@ -160,44 +247,34 @@ def rope_apply(x, cos, sin, head_dim):
     return out
 
 
-def gemm(a, w, bias=None, epilogue=EPI_BIAS, resid=None, gate=None, out=None):
-    """out[M,N] = epilogue(a[M,K] @ w[N,K]^T + bias) — gf_gemm_bf16."""
-    _req(a, "gemm.a")
-    _req(w, "gemm.w")
-    av, M, K, lda = _rows2d(a, "gemm.a")
-    if w.dim() != 2 or w.stride(1) != 1 or w.shape[1] != K:
-        raise GoalForceError(f"gemm.w: expected [N, {K}] with contiguous rows, got {tuple(w.shape)}")
-    N = w.shape[0]
+def _gemm(a, w, row_scale, bias, epilogue, resid, gate, out):
+    """gemm (row_scale None) and gemm_fp8: one set of checks, then gf_gemm_bf16 / gf_gemm_fp8 (which takes the row scales after ldw).
+    The names in its errors are constants (the wrappers run thousands of times per denoise step)."""
+    av, M, K, lda, N, ldw = _linear_operands(a, w, row_scale)
     if out is None:
         out = torch.empty(a.shape[:-1] + (N,), dtype=_BF16, device=a.device)
-    ov, Mo, No, ldc = _rows2d(out, "gemm.out")
+    ov, Mo, No, ldc = _rows2d(out, "gemm[_fp8].out")
     if (Mo, No) != (M, N):
-        raise GoalForceError(f"gemm.out: expected [{M}, {N}], got [{Mo}, {No}]")
+        raise GoalForceError(f"gemm[_fp8].out: expected [{M}, {N}], got [{Mo}, {No}]")
     ldr = 0
     if resid is not None:
-        _req(resid, "gemm.resid")
-        rv, Mr, Nr, ldr = _rows2d(resid, "gemm.resid")
+        _req(resid, "gemm[_fp8].resid")
+        resid, Mr, Nr, ldr = _rows2d(resid, "gemm[_fp8].resid")
         if (Mr, Nr) != (M, N):
-            raise GoalForceError("gemm.resid: shape mismatch")
-        resid = rv
-    if gate is not None:
-        _req(gate, "gemm.gate")
-        if gate.numel() != N or not gate.is_contiguous():
-            raise GoalForceError(f"gemm.gate: expected contiguous [{N}]")
-    if bias is not None:
-        _req(bias, "gemm.bias")
-        if bias.numel() != N or not bias.is_contiguous():
-            raise GoalForceError(f"gemm.bias: expected contiguous [{N}]")
-    prof = PROFILE_GEMM
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    _lib.check(_lib.load().gf_gemm_bf16(_ptr(av), lda, _ptr(w), w.stride(0), _ptr(bias), _ptr(ov), ldc, M, N, K,
-                                        int(epilogue), _ptr(resid), ldr, _ptr(gate), _stream(a)), "gf_gemm_bf16")
-    if prof is not None:
-        e1.record()
-        prof.append((e0, e1, M, N, K, int(epilogue)))
+            raise GoalForceError(f"gemm[_fp8].resid: expected [{M}, {N}], got [{Mr}, {Nr}]")
+    _vec(gate, "gemm[_fp8].gate", N)
+    _vec(bias, "gemm[_fp8].bias", N)
+    lib = _lib.load()
+    fn, scale = (lib.gf_gemm_bf16, ()) if row_scale is None else (lib.gf_gemm_fp8, (_ptr(row_scale),))
+    with _timed(PROFILE_GEMM, M, N, K, int(epilogue)):
+        _lib.check(fn(_ptr(av), lda, _ptr(w), ldw, *scale, _ptr(bias), _ptr(ov), ldc, M, N, K, int(epilogue), _ptr(resid), ldr,
+                      _ptr(gate), _stream(a)), fn.__name__)
     return out
+
+
+def gemm(a, w, bias=None, epilogue=EPI_BIAS, resid=None, gate=None, out=None):
+    """out[M,N] = epilogue(a[M,K] @ w[N,K]^T + bias) — gf_gemm_bf16."""
+    return _gemm(a, w, None, bias, epilogue, resid, gate, out)
 
 
 VT_MIN_KV = 2048   # key sequences at least this long go through the pre-transposed-V kernel (kernel 3)
@@ -276,55 +353,51 @@ def _vt_workspace(numel, device):
     return ws
 
 
+def _vt_shape(skv, num_heads, head_dim):
+    """The shapes of the pre-transposed-V kernels (2 and 3): long key sequences at head_dim 128 whose V^T fits 31-bit indices."""
+    return skv >= VT_MIN_KV and head_dim == 128 and num_heads * 128 * kv_pad(skv) < 2 ** 31
+
+
 def vt32_ok(skv, num_heads, head_dim):
     """True when flash_attn would take the pre-transposed-V kernel 3 for this key length (then linear_vt32 can produce its V^T)."""
-    kv_pad = -(-skv // 64) * 64
-    return (skv >= VT_MIN_KV and head_dim == 128 and num_heads * 128 * kv_pad < 2 ** 31
-            and _OPT["attn_k3"] and _OPT["vt_from_gemm"])
+    return _vt_shape(skv, num_heads, head_dim) and _OPT["attn_k3"] and _OPT["vt_from_gemm"]
+
+
+def _linear_vt32(x, w, x_scale, bias):
+    """linear_vt32 (x_scale None) and linear_vt32_fp8: gf_linear_vt32 / gf_linear_vt32_fp8 (which takes the row scales after ldx)."""
+    xv, skv, K, ldx, N, ldw = _linear_operands(x, w, x_scale)
+    _vec(bias, "linear_vt32[_fp8].bias", N)
+    vt = _vt_workspace(N * kv_pad(skv), x.device)
+    lib = _lib.load()
+    fn, scale = (lib.gf_linear_vt32, ()) if x_scale is None else (lib.gf_linear_vt32_fp8, (_ptr(x_scale),))
+    _lib.check(fn(_ptr(xv), ldx, *scale, _ptr(w), ldw, _ptr(bias), _ptr(vt), skv, kv_pad(skv), N, K, _stream(x)), fn.__name__)
+    return vt
 
 
 def linear_vt32(x, weight, bias):
     """The V projection of a self-attention, written directly as kernel 3's V^T operand (gf_linear_vt32): returns the V^T
     workspace of this (device, stream) — valid until the next call — for flash_attn(..., vt=...).  Same bits as
     gemm(x, weight, bias) followed by the transpose inside flash_attn."""
-    _req(x, "linear_vt32.x")
-    _req(weight, "linear_vt32.weight")
-    xv, skv, K, ldx = _rows2d(x, "linear_vt32.x")
-    if weight.dim() != 2 or weight.stride(1) != 1 or weight.shape[1] != K:
-        raise GoalForceError(f"linear_vt32.weight: expected [N, {K}] with contiguous rows")
-    N = weight.shape[0]
-    if bias is not None:
-        _req(bias, "linear_vt32.bias")
-        if bias.numel() != N or not bias.is_contiguous():
-            raise GoalForceError(f"linear_vt32.bias: expected contiguous [{N}]")
-    kv_pad = -(-skv // 64) * 64
-    vt = _vt_workspace(N * kv_pad, x.device)
-    _lib.check(_lib.load().gf_linear_vt32(_ptr(xv), ldx, _ptr(weight), weight.stride(0), _ptr(bias), _ptr(vt), skv, kv_pad, N, K,
-                                          _stream(x)), "gf_linear_vt32")
-    return vt
+    return _linear_vt32(x, weight, None, bias)
 
 
 def linear_vt32_fp8(x8, x_scale, w8, bias):
     """linear_vt32 on the fp8_linear contract (config 5): x8 [S, K] float8_e4m3fn + its row scales, w8 [N, K] float8_e4m3fn ->
     the V^T workspace (gf_linear_vt32_fp8); same bits as gemm_fp8(x8, x_scale, w8, bias) followed by the transpose."""
-    _req(x8, "linear_vt32_fp8.x8", _FP8)
-    _req(w8, "linear_vt32_fp8.w8", _FP8)
-    _req(x_scale, "linear_vt32_fp8.x_scale", torch.float32)
-    if x8.dim() != 2 or w8.dim() != 2 or x8.stride(1) != 1 or w8.stride(1) != 1 or x8.shape[1] != w8.shape[1]:
-        raise GoalForceError("linear_vt32_fp8: x8 [S,K], w8 [N,K] with contiguous rows expected")
-    skv, K = x8.shape
-    N = w8.shape[0]
-    if x_scale.numel() != skv or not x_scale.is_contiguous():
-        raise GoalForceError("linear_vt32_fp8.x_scale: contiguous [S] expected")
-    if bias is not None:
-        _req(bias, "linear_vt32_fp8.bias")
-        if bias.numel() != N or not bias.is_contiguous():
-            raise GoalForceError(f"linear_vt32_fp8.bias: expected contiguous [{N}]")
-    kv_pad = -(-skv // 64) * 64
-    vt = _vt_workspace(N * kv_pad, x8.device)
-    _lib.check(_lib.load().gf_linear_vt32_fp8(_ptr(x8), x8.stride(0), _ptr(x_scale), _ptr(w8), w8.stride(0), _ptr(bias), _ptr(vt), skv,
-                                              kv_pad, N, K, _stream(x8)), "gf_linear_vt32_fp8")
-    return vt
+    if x_scale is None:
+        raise GoalForceError("linear_vt32_fp8.x_scale: required")
+    return _linear_vt32(x8, w8, x_scale, bias)
+
+
+def _vt_attn(lib, q, k, v, vt, out, lse, sq, skv, num_heads, head_dim, scale, k3):
+    """The attention over a pre-transposed V, shared by flash_attn and flash_attn_lse: kernel 3 (16x16x32 MFMAs), or (k3 False:
+    options(attn_k3=False) for the cross-check tests, a finished q) kernel 2 (32x32x16).  vt None: V^T is made here from v."""
+    tr, fa = (lib.gf_transpose_v32, lib.gf_flash_attn_fwd_vt32) if k3 else (lib.gf_transpose_v, lib.gf_flash_attn_fwd_vt)
+    if vt is None:
+        vt = _vt_workspace(num_heads * 128 * kv_pad(skv), q.device)
+        _lib.check(tr(_ptr(v), v.stride(0), _ptr(vt), skv, kv_pad(skv), num_heads, _stream(q)), "gf_transpose_v")
+    _lib.check(fa(_ptr(q), _ptr(k), _ptr(vt), _ptr(out), _ptr(lse), sq, skv, kv_pad(skv), num_heads, head_dim,
+                  q.stride(0), k.stride(0), out.stride(0), float(scale), _stream(q)), "gf_flash_attn_fwd_vt")
 
 
 def flash_attn(q, k, v, num_heads, out=None, scale=None, vt=None, last_key_mult=1, finished_q=False):
@@ -337,9 +410,7 @@ def flash_attn(q, k, v, num_heads, out=None, scale=None, vt=None, last_key_mult=
     cannot: long key sequences then run on kernel 2, which scales the fp32 scores (2.1e-3 / 1.9e-3; +16 % time at S = 32760,
     profiles/r06/b3_precision.log)."""
     for n, t in (("q", q), ("k", k)) + ((("v", v),) if vt is None else ()):
-        _req(t, f"flash_attn.{n}")
-        if t.dim() != 2 or t.stride(1) != 1:
-            raise GoalForceError(f"flash_attn.{n}: expected 2-D [len, heads*head_dim] with contiguous rows")
+        _mat(t, f"flash_attn.{n}")
     sq, hd_all = q.shape
     skv = k.shape[0]
     head_dim = hd_all // num_heads
@@ -351,40 +422,27 @@ def flash_attn(q, k, v, num_heads, out=None, scale=None, vt=None, last_key_mult=
         out = torch.empty((sq, hd_all), dtype=_BF16, device=q.device)
     if scale is None:
         scale = 1.0 / math.sqrt(head_dim)
-    prof = PROFILE_ATTN
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    lib = _lib.load()
-    kv_pad = -(-skv // 64) * 64
     if last_key_mult != 1 and (vt is not None or skv >= VT_MIN_KV):
         raise GoalForceError("flash_attn: last_key_mult is for short key sequences (the text context), not the V^T path")
-    if skv >= VT_MIN_KV and head_dim == 128 and num_heads * 128 * kv_pad < 2 ** 31:
-        # long key sequences (the DiT self-attention): hand V over pre-transposed — one LDS read per PV MFMA instead of two;
-        # the transpose (0.7 % of the attention's time at S=32760) is inside the timed region
-        # kernel 3 (16x16x32 MFMAs); options(attn_k3=False) sends the shape to kernel 2 (32x32x16) for the cross-check tests
-        if finished_q and vt is not None:
-            raise GoalForceError("flash_attn: finished_q goes to kernel 2, which does not take kernel 3's V^T operand")
-        k3 = _OPT["attn_k3"] and not finished_q
-        tr, fa = (lib.gf_transpose_v32, lib.gf_flash_attn_fwd_vt32) if k3 else (lib.gf_transpose_v, lib.gf_flash_attn_fwd_vt)
-        if vt is None:
-            vt = _vt_workspace(num_heads * 128 * kv_pad, q.device)
-            _lib.check(tr(_ptr(v), v.stride(0), _ptr(vt), skv, kv_pad, num_heads, _stream(q)), "gf_transpose_v")
-        elif vt.numel() < num_heads * 128 * kv_pad:
-            raise GoalForceError("flash_attn.vt: buffer smaller than heads*128*kv_pad")
-        _lib.check(fa(_ptr(q), _ptr(k), _ptr(vt), _ptr(out), None, sq, skv, kv_pad, num_heads, head_dim,
-                      q.stride(0), k.stride(0), out.stride(0), float(scale), _stream(q)), "gf_flash_attn_fwd_vt")
-    elif last_key_mult != 1:
-        _lib.check(lib.gf_flash_attn_fwd_lastmult(_ptr(q), _ptr(k), _ptr(v), _ptr(out), sq, skv, num_heads, head_dim, q.stride(0),
-                                                  k.stride(0), v.stride(0), out.stride(0), float(scale), float(last_key_mult), _stream(q)),
-                   "gf_flash_attn_fwd_lastmult")
-    else:
-        _lib.check(lib.gf_flash_attn_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), sq, skv, num_heads, head_dim,
-                                         q.stride(0), k.stride(0), v.stride(0), out.stride(0), float(scale),
-                                         _stream(q)), "gf_flash_attn_fwd")
-    if prof is not None:
-        e1.record()
-        prof.append((e0, e1, sq, skv, num_heads))
+    long_keys = _vt_shape(skv, num_heads, head_dim)
+    if finished_q and vt is not None:
+        raise GoalForceError("flash_attn: finished_q goes to kernel 2, which does not take kernel 3's V^T operand")
+    if vt is not None and vt.numel() < num_heads * 128 * kv_pad(skv):
+        raise GoalForceError("flash_attn.vt: buffer smaller than heads*128*kv_pad")
+    lib = _lib.load()
+    with _timed(PROFILE_ATTN, sq, skv, num_heads):
+        if long_keys:
+            # long key sequences (the DiT self-attention): hand V over pre-transposed — one LDS read per PV MFMA instead of two;
+            # the transpose (0.7 % of the attention's time at S=32760) is inside the timed region
+            _vt_attn(lib, q, k, v, vt, out, None, sq, skv, num_heads, head_dim, scale, _OPT["attn_k3"] and not finished_q)
+        elif last_key_mult != 1:
+            _lib.check(lib.gf_flash_attn_fwd_lastmult(_ptr(q), _ptr(k), _ptr(v), _ptr(out), sq, skv, num_heads, head_dim, q.stride(0),
+                                                      k.stride(0), v.stride(0), out.stride(0), float(scale), float(last_key_mult),
+                                                      _stream(q)), "gf_flash_attn_fwd_lastmult")
+        else:
+            _lib.check(lib.gf_flash_attn_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(out), sq, skv, num_heads, head_dim,
+                                             q.stride(0), k.stride(0), v.stride(0), out.stride(0), float(scale),
+                                             _stream(q)), "gf_flash_attn_fwd")
     return out
 
 
@@ -397,9 +455,7 @@ _SAGE_SCRATCH_PER_HEAD = 64 * 128 * 8
 
 def _sage_rows(t, name, num_heads):
     """A [rows, >= heads*128] bf16 operand with contiguous rows (a column slice of a wider tensor is fine) -> (rows, row stride)."""
-    _req(t, name)
-    if t.dim() != 2 or t.stride(1) != 1:
-        raise GoalForceError(f"{name}: expected 2-D [len, heads*128] with contiguous rows")
+    _mat(t, name)
     if t.shape[1] != num_heads * 128:
         raise GoalForceError(f"{name}: {t.shape[1]} columns for {num_heads} heads: the sage backend is built for head_dim 128")
     if t.shape[0] < 1:
@@ -445,9 +501,7 @@ def sage_quant_k(k, num_heads, mu=None):
     skv, ldk = _sage_rows(k, "sage_quant_k.k", num_heads)
     if mu is None:
         mu = sage_k_mean(k, num_heads)
-    _req(mu, "sage_quant_k.mu", torch.float32)
-    if mu.numel() != num_heads * 128 or not mu.is_contiguous():
-        raise GoalForceError("sage_quant_k.mu: contiguous [heads, 128] fp32 expected")
+    _vec(mu, "sage_quant_k.mu", num_heads * 128, torch.float32)
     kv_pad8 = -(-skv // SAGE_T) * SAGE_T
     k8 = torch.empty((kv_pad8, num_heads * 128), dtype=torch.int8, device=k.device)
     sc = torch.empty((num_heads, kv_pad8 // SAGE_KBLK), dtype=torch.float32, device=k.device)
@@ -466,7 +520,7 @@ def sage_quant_vt(v, num_heads, vt=None, kv_len=None):
         _req(vt, "sage_quant_vt.vt")
         if kv_len is None or kv_len < 1:
             raise GoalForceError("sage_quant_vt: a V^T input needs kv_len")
-        skv, ldv, src, vt_in = kv_len, -(-kv_len // 64) * 64, vt, 1
+        skv, ldv, src, vt_in = kv_len, kv_pad(kv_len), vt, 1
         if vt.numel() < num_heads * 128 * ldv:
             raise GoalForceError("sage_quant_vt.vt: buffer smaller than heads*128*kv_pad")
     kv_pad8 = -(-skv // SAGE_T) * SAGE_T
@@ -503,28 +557,21 @@ def sage_attn(q, k, v, num_heads, scale=None, vt=None, out=None):
         src, vt_in = v, 0
     else:
         _req(vt, "sage_attn.vt")
-        ldv, src, vt_in = -(-skv // 64) * 64, vt, 1
+        ldv, src, vt_in = kv_pad(skv), vt, 1
         if vt.numel() < num_heads * 128 * ldv:
             raise GoalForceError("sage_attn.vt: buffer smaller than heads*128*kv_pad")
-    if out is None:
-        out = torch.empty((sq, num_heads * 128), dtype=_BF16, device=q.device)
-    elif out.dtype != _BF16 or out.dim() != 2 or out.stride(1) != 1 or tuple(out.shape) != (sq, num_heads * 128) or out.stride(0) % 8:
-        raise GoalForceError(f"sage_attn.out: bf16 [{sq}, {num_heads * 128}] with contiguous rows expected")
+    out = _out(out, "sage_attn.out", sq, num_heads * 128, q.device)
+    if out.stride(0) % 8:
+        raise GoalForceError("sage_attn.out: row stride must be a multiple of 8 elements")
     lib = _lib.load()
     nbytes = int(lib.gf_sage_workspace_bytes(sq, skv, num_heads))
     key = (q.device.index, torch.cuda.current_stream(q.device).cuda_stream)
     ws = _SAGE_WS.get(key)
     if ws is None or ws.numel() < nbytes:
         ws = _SAGE_WS[key] = torch.empty((nbytes,), dtype=torch.uint8, device=q.device)
-    prof = PROFILE_ATTN
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    _lib.check(lib.gf_sage_attn(_ptr(q), ldq, _ptr(k), ldk, _ptr(src), ldv, vt_in, _ptr(out), out.stride(0), sq, skv, num_heads, scale,
-                                _ptr(ws), _stream(q)), "gf_sage_attn")
-    if prof is not None:
-        e1.record()
-        prof.append((e0, e1, sq, skv, num_heads))
+    with _timed(PROFILE_ATTN, sq, skv, num_heads):
+        _lib.check(lib.gf_sage_attn(_ptr(q), ldq, _ptr(k), ldk, _ptr(src), ldv, vt_in, _ptr(out), out.stride(0), sq, skv, num_heads,
+                                    scale, _ptr(ws), _stream(q)), "gf_sage_attn")
     return out
 
 
@@ -535,19 +582,14 @@ def cross_probs(q, k, num_heads, n_pad, last_key_mult=1, scale=None, out=None):
     """The normalised probabilities of softmax(q k^T / sqrt(d)) per head instead of the attention output (gf_cross_probs):
     q [Sq, H*128], k [n_keys <= 63, H*128] (row-strided views OK) -> [Sq, H*n_pad] bf16 (n_pad > n_keys), column h*n_pad + j = key j
     of head h; column n_keys: the last key's rounding residue bf16(w - bf16(w)); zero after it.  `last_key_mult` as in flash_attn.  With U = cross_fold_table(v, w_o, H, n_pad), P @ U^T = flash_attn(q, k, v) @ w_o^T."""
-    for n, t in (("q", q), ("k", k)):
-        _req(t, f"cross_probs.{n}")
-        if t.dim() != 2 or t.stride(1) != 1:
-            raise GoalForceError(f"cross_probs.{n}: expected 2-D [len, heads*head_dim] with contiguous rows")
+    _mat(q, "cross_probs.q")
+    _mat(k, "cross_probs.k")
     sq, hd_all = q.shape
     n_keys = k.shape[0]
     head_dim = hd_all // num_heads
     if k.shape[1] != hd_all or head_dim * num_heads != hd_all:
         raise GoalForceError("cross_probs: q/k shape mismatch")
-    if out is None:
-        out = torch.empty((sq, num_heads * n_pad), dtype=_BF16, device=q.device)
-    elif out.dtype != _BF16 or out.dim() != 2 or out.stride(1) != 1 or tuple(out.shape) != (sq, num_heads * n_pad):
-        raise GoalForceError(f"cross_probs.out: expected [{sq}, {num_heads * n_pad}] bf16 with contiguous rows")
+    out = _out(out, "cross_probs.out", sq, num_heads * n_pad, q.device)
     if scale is None:
         scale = 1.0 / math.sqrt(head_dim)
     _lib.check(_lib.load().gf_cross_probs(_ptr(q), _ptr(k), _ptr(out), sq, n_keys, n_pad, num_heads, head_dim, q.stride(0), k.stride(0),
@@ -559,26 +601,21 @@ def cross_fold_table(v, w_o, num_heads, n_pad):
     """The value table of cross_probs (gf_cross_fold_table): U [N, H*n_pad] bf16, U[n, h*n_pad + j] = sum_d v[j, h*128+d] w_o[n, h*128+d]
     (fp32 accumulation, one rounding) for j < n_keys, column n_keys = column n_keys - 1 (the partner of cross_probs' residue column),
     zero after it — the [N, K] weight layout gemm takes."""
-    for n, t in (("v", v), ("w_o", w_o)):
-        _req(t, f"cross_fold_table.{n}")
-        if t.dim() != 2 or t.stride(1) != 1:
-            raise GoalForceError(f"cross_fold_table.{n}: expected 2-D with contiguous rows")
+    _mat(v, "cross_fold_table.v")
     n_keys, hd_all = v.shape
-    if w_o.shape[1] != hd_all or hd_all % num_heads:
-        raise GoalForceError("cross_fold_table: v / w_o shape mismatch")
-    N = w_o.shape[0]
+    N, ldw = _weight(w_o, "cross_fold_table.w_o", hd_all)
+    if hd_all % num_heads:
+        raise GoalForceError(f"cross_fold_table: {hd_all} columns do not divide into {num_heads} heads")
     u = torch.empty((N, num_heads * n_pad), dtype=_BF16, device=v.device)
     _lib.check(_lib.load().gf_cross_fold_table(_ptr(v), _ptr(w_o), _ptr(u), n_keys, n_pad, num_heads, hd_all // num_heads, N, v.stride(0),
-                                               w_o.stride(0), u.stride(0), _stream(v)), "gf_cross_fold_table")
+                                               ldw, u.stride(0), _stream(v)), "gf_cross_fold_table")
     return u
 
 
 def flash_attn_lse(q, k, v, num_heads, scale=None):
     """flash_attn that also returns the log2-domain log-sum-exp [Sq, H] fp32 (what flash_attn_bwd rebuilds P from)."""
     for n, t in (("q", q), ("k", k), ("v", v)):
-        _req(t, f"flash_attn_lse.{n}")
-        if t.dim() != 2 or t.stride(1) != 1:
-            raise GoalForceError(f"flash_attn_lse.{n}: expected 2-D [len, heads*head_dim] with contiguous rows")
+        _mat(t, f"flash_attn_lse.{n}")
     sq, hd_all = q.shape
     skv = k.shape[0]
     head_dim = hd_all // num_heads
@@ -589,14 +626,8 @@ def flash_attn_lse(q, k, v, num_heads, scale=None):
     out = torch.empty((sq, hd_all), dtype=_BF16, device=q.device)
     lse = torch.empty((sq, num_heads), dtype=torch.float32, device=q.device)
     lib = _lib.load()
-    kv_pad = -(-skv // 64) * 64
-    if skv >= VT_MIN_KV and head_dim == 128 and num_heads * 128 * kv_pad < 2 ** 31:   # as flash_attn: pre-transposed V, same bits
-        vt = _vt_workspace(num_heads * 128 * kv_pad, q.device)
-        k3 = _OPT["attn_k3"]
-        tr, fa = (lib.gf_transpose_v32, lib.gf_flash_attn_fwd_vt32) if k3 else (lib.gf_transpose_v, lib.gf_flash_attn_fwd_vt)
-        _lib.check(tr(_ptr(v), v.stride(0), _ptr(vt), skv, kv_pad, num_heads, _stream(q)), "gf_transpose_v")
-        _lib.check(fa(_ptr(q), _ptr(k), _ptr(vt), _ptr(out), _ptr(lse), sq, skv, kv_pad, num_heads, head_dim,
-                      q.stride(0), k.stride(0), out.stride(0), float(scale), _stream(q)), "gf_flash_attn_fwd_vt")
+    if _vt_shape(skv, num_heads, head_dim):   # as flash_attn: pre-transposed V, same bits
+        _vt_attn(lib, q, k, v, None, out, lse, sq, skv, num_heads, head_dim, scale, _OPT["attn_k3"])
         return out, lse
     _lib.check(lib.gf_flash_attn_fwd_lse(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse), sq, skv, num_heads, head_dim,
                                          q.stride(0), k.stride(0), v.stride(0), out.stride(0), float(scale),
@@ -608,9 +639,7 @@ def flash_attn_bwd(q, k, v, o, dout, lse, num_heads, scale=None, need_dkv=True):
     """Gradients of flash_attn: (dq [Sq, H*128], dk, dv [Skv, H*128]) bf16; need_dkv=False: (dq, None, None) — the dK/dV kernel is
     not launched (a frozen block's cross-attention: nobody reads the gradients of the text context)."""
     for n, t in (("q", q), ("k", k), ("v", v), ("o", o), ("dout", dout)):
-        _req(t, f"flash_attn_bwd.{n}")
-        if t.dim() != 2 or t.stride(1) != 1:
-            raise GoalForceError(f"flash_attn_bwd.{n}: expected 2-D [len, heads*head_dim] with contiguous rows")
+        _mat(t, f"flash_attn_bwd.{n}")
     sq, hd_all = q.shape
     skv = k.shape[0]
     head_dim = hd_all // num_heads
@@ -664,37 +693,26 @@ def unpatchify(tokens, c, f, h, w):
 
 def cfg_euler_step(latents, posi, nega, cfg_scale, dsigma):
     """In place: latents += (nega + cfg*(posi-nega)) * dsigma with bf16 rounding after every op."""
-    _req(latents, "cfg_euler_step.latents")
-    _req(posi, "cfg_euler_step.posi")
-    if not latents.is_contiguous() or not posi.is_contiguous() or posi.numel() != latents.numel():
-        raise GoalForceError("cfg_euler_step: latents/posi must be contiguous and equal-sized")
-    if nega is not None:
-        _req(nega, "cfg_euler_step.nega")
-        if not nega.is_contiguous() or nega.numel() != latents.numel():
-            raise GoalForceError("cfg_euler_step: nega must be contiguous and equal-sized")
-    _lib.check(_lib.load().gf_cfg_euler_step(_ptr(latents), _ptr(posi), _ptr(nega), float(cfg_scale), float(dsigma),
-                                             latents.numel(), _stream(latents)), "gf_cfg_euler_step")
+    if posi is None:
+        raise GoalForceError("cfg_euler_step.posi: required")
+    n = _flat("cfg_euler_step", latents=latents, posi=posi, nega=nega)
+    _lib.check(_lib.load().gf_cfg_euler_step(_ptr(latents), _ptr(posi), _ptr(nega), float(cfg_scale), float(dsigma), n,
+                                             _stream(latents)), "gf_cfg_euler_step")
     return latents
 
 
 def act(x, kind: str):
-    _req(x, "act.x")
-    if not x.is_contiguous():
-        raise GoalForceError("act.x must be contiguous")
+    n = _flat("act", x=x)
     out = torch.empty_like(x)
-    _lib.check(_lib.load().gf_act(_ptr(x), _ptr(out), x.numel(), {"silu": 0, "gelu_tanh": 1}[kind], _stream(x)),
-               "gf_act")
+    _lib.check(_lib.load().gf_act(_ptr(x), _ptr(out), n, {"silu": 0, "gelu_tanh": 1}[kind], _stream(x)), "gf_act")
     return out
 
 
 def add(a, b, out=None):
-    _req(a, "add.a")
-    _req(b, "add.b")
-    if not a.is_contiguous() or not b.is_contiguous() or a.numel() != b.numel():
-        raise GoalForceError("add: a/b must be contiguous and equal-sized")
+    n = _flat("add", a=a, b=b)
     if out is None:
         out = torch.empty_like(a)
-    _lib.check(_lib.load().gf_add_bf16(_ptr(a), _ptr(b), _ptr(out), a.numel(), _stream(a)), "gf_add_bf16")
+    _lib.check(_lib.load().gf_add_bf16(_ptr(a), _ptr(b), _ptr(out), n, _stream(a)), "gf_add_bf16")
     return out
 
 
@@ -729,22 +747,41 @@ def vae_prep_latent(z_slice, mean, inv_std, cpad=64):
     return out
 
 
-def vae_im2col(src, cache, kt, ks, kpad, upsample2x=False, downsample2=False, t_stride=1, t_off=0, t_out=None):
-    """src [T,H,W,C] (+cache [2,H,W,C]) -> [T_out*Ho*Wo, kpad] patch matrix (modes: see gf_vae_im2col)."""
-    _req(src, "vae_im2col.src")
-    if not src.is_contiguous():
-        raise GoalForceError("vae_im2col.src must be contiguous [T,H,W,C]")
+def _conv_window(op, src, cache, upsample2x, downsample2, t_stride, t_off, t_out):
+    """The gather of vae_im2col / vae_conv3d: src [T,H,W,C] contiguous (+ cache [2,H,W,C]) and the temporal window
+    -> (mode, t_out, output pixels per frame); modes: see gf_vae_im2col."""
+    _req(src, f"{op}.src")
+    if src.dim() != 4 or not src.is_contiguous():
+        raise GoalForceError(f"{op}.src must be contiguous [T,H,W,C]")
     T, H, W, C = src.shape
     if cache is not None:
-        _req(cache, "vae_im2col.cache")
+        _req(cache, f"{op}.cache")
         if tuple(cache.shape) != (2, H, W, C) or not cache.is_contiguous():
-            raise GoalForceError(f"vae_im2col.cache must be contiguous [2,{H},{W},{C}]")
+            raise GoalForceError(f"{op}.cache must be contiguous [2,{H},{W},{C}]")
     mode = 1 if upsample2x else (2 if downsample2 else 0)
     if t_out is None:
         t_out = (T - t_off + t_stride - 1) // t_stride
     if t_off + (t_out - 1) * t_stride >= T:
-        raise GoalForceError("vae_im2col: temporal window exceeds the source")
-    px = H * W * 4 if mode == 1 else ((H // 2) * (W // 2) if mode == 2 else H * W)
+        raise GoalForceError(f"{op}: temporal window exceeds the source")
+    return mode, t_out, H * W * 4 if mode == 1 else ((H // 2) * (W // 2) if mode == 2 else H * W)
+
+
+def _conv_resid(op, rows, bias, resid):
+    """The epilogue operands of the VAE convolutions: bias bf16; resid [rows, >= N] with contiguous rows -> its row stride (0: none)."""
+    if bias is not None:
+        _req(bias, f"{op}.bias")
+    if resid is None:
+        return 0
+    _mat(resid, f"{op}.resid")
+    if resid.shape[0] != rows:
+        raise GoalForceError(f"{op}.resid must be [{rows}, >= N] with contiguous rows")
+    return resid.stride(0)
+
+
+def vae_im2col(src, cache, kt, ks, kpad, upsample2x=False, downsample2=False, t_stride=1, t_off=0, t_out=None):
+    """src [T,H,W,C] (+cache [2,H,W,C]) -> [T_out*Ho*Wo, kpad] patch matrix (modes: see gf_vae_im2col)."""
+    mode, t_out, px = _conv_window("vae_im2col", src, cache, upsample2x, downsample2, t_stride, t_off, t_out)
+    T, H, W, C = src.shape
     out = torch.empty((t_out * px, kpad), dtype=_BF16, device=src.device)
     _lib.check(_lib.load().gf_vae_im2col(_ptr(src), _ptr(cache), _ptr(out), t_out, H, W, C, kt, ks, mode, t_stride, t_off,
                                          kpad, _stream(src)), "gf_vae_im2col")
@@ -757,10 +794,7 @@ def vae_conv3d(src, cache, w, bias, kt, ks, upsample2x=False, downsample2=False,
     Same arguments as vae_im2col + gemm(epilogue BIAS / BIAS_RESID); bit-identical to that pair.
     history_in_front: src is frames [2:] of one contiguous [2+T,H,W,C] buffer whose first two frames hold the causal history
     (pass cache=None): the faster pointer-per-row gather."""
-    _req(src, "vae_conv3d.src")
-    _req(w, "vae_conv3d.w")
-    if not src.is_contiguous() or src.dim() != 4:
-        raise GoalForceError("vae_conv3d.src must be contiguous [T,H,W,C]")
+    mode, t_out, px = _conv_window("vae_conv3d", src, cache, upsample2x, downsample2, t_stride, t_off, t_out)
     T, H, W, C = src.shape
     if kt == 3:
         if history_in_front:
@@ -768,40 +802,15 @@ def vae_conv3d(src, cache, w, bias, kt, ks, upsample2x=False, downsample2=False,
                 raise GoalForceError("vae_conv3d: history_in_front needs cache=None and src = buffer[2:] of a [2+T,H,W,C] buffer")
         elif cache is None:
             raise GoalForceError("vae_conv3d: a temporal kernel needs its 2-frame cache (or history_in_front)")
-    if cache is not None:
-        _req(cache, "vae_conv3d.cache")
-        if tuple(cache.shape) != (2, H, W, C) or not cache.is_contiguous():
-            raise GoalForceError(f"vae_conv3d.cache must be contiguous [2,{H},{W},{C}]")
-    if w.dim() != 2 or w.stride(1) != 1:
-        raise GoalForceError("vae_conv3d.w must be [N, kpad] with contiguous rows")
-    mode = 1 if upsample2x else (2 if downsample2 else 0)
-    if t_out is None:
-        t_out = (T - t_off + t_stride - 1) // t_stride
-    px = H * W * 4 if mode == 1 else ((H // 2) * (W // 2) if mode == 2 else H * W)
+    _mat(w, "vae_conv3d.w")
     n, k = w.shape
-    if out is None:
-        out = torch.empty((t_out * px, n), dtype=_BF16, device=src.device)
-    elif out.dim() != 2 or out.shape != (t_out * px, n) or out.stride(1) != 1:
-        raise GoalForceError("vae_conv3d.out must be [T_out*Ho*Wo, N] with contiguous rows")
-    if bias is not None:
-        _req(bias, "vae_conv3d.bias")
-    ldr = 0
-    if resid is not None:
-        _req(resid, "vae_conv3d.resid")
-        if resid.dim() != 2 or resid.shape[0] != t_out * px or resid.stride(1) != 1:
-            raise GoalForceError("vae_conv3d.resid must be [T_out*Ho*Wo, >=N] with contiguous rows")
-        ldr = resid.stride(0)
-    prof = PROFILE_CONV
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    _lib.check(_lib.load().gf_conv3d_bf16(_ptr(src), _ptr(cache), _ptr(w), w.stride(0), _ptr(bias), _ptr(out), out.stride(0),
-                                          T, t_out, H, W, C, kt, ks, mode, t_stride, t_off, n, k,
-                                          EPI_BIAS if resid is None else EPI_BIAS_RESID, _ptr(resid), ldr, _stream(src)),
-               "gf_conv3d_bf16")
-    if prof is not None:
-        e1.record()
-        prof.append((e0, e1, t_out * px, n, C, kt, ks, mode, resid is not None))
+    out = _out(out, "vae_conv3d.out", t_out * px, n, src.device)
+    ldr = _conv_resid("vae_conv3d", t_out * px, bias, resid)
+    with _timed(PROFILE_CONV, t_out * px, n, C, kt, ks, mode, resid is not None):
+        _lib.check(_lib.load().gf_conv3d_bf16(_ptr(src), _ptr(cache), _ptr(w), w.stride(0), _ptr(bias), _ptr(out), out.stride(0),
+                                              T, t_out, H, W, C, kt, ks, mode, t_stride, t_off, n, k,
+                                              EPI_BIAS if resid is None else EPI_BIAS_RESID, _ptr(resid), ldr, _stream(src)),
+                   "gf_conv3d_bf16")
     return out
 
 
@@ -855,43 +864,25 @@ def vae_conv3d_padded(buf, w, bias, resid=None, out=None, kt=3):
     3x3 convolution per frame on `buf` [T, H + 2, W + 2, C].  x w [N, >= 9 kt C] -> [T*H*W, N]; resid [T*H*W, >= N] is added after
     the bf16 rounding of conv + bias.  Bit-identical to vae_conv3d."""
     _req(buf, "vae_conv3d_padded.buf")
-    _req(w, "vae_conv3d_padded.w")
     if buf.dim() != 4 or not buf.is_contiguous() or kt not in (1, 3):
         raise GoalForceError("vae_conv3d_padded.buf must be contiguous [kt-1+T, H+2, W+2, C], kt = 1 or 3")
     T, H, W, C = buf.shape[0] - (kt - 1), buf.shape[1] - 2, buf.shape[2] - 2, buf.shape[3]
+    _mat(w, "vae_conv3d_padded.w")
     n = w.shape[0]
-    if w.dim() != 2 or w.stride(1) != 1 or w.shape[1] < 9 * kt * C:
+    if w.shape[1] < 9 * kt * C:
         raise GoalForceError("vae_conv3d_padded.w must be [N, >= 9 kt C] with contiguous rows")
-    if out is None:
-        out = torch.empty((T * H * W, n), dtype=_BF16, device=buf.device)
-    elif out.dim() != 2 or out.shape != (T * H * W, n) or out.stride(1) != 1:
-        raise GoalForceError("vae_conv3d_padded.out must be [T*H*W, N] with contiguous rows")
-    ldr = 0
-    if bias is not None:
-        _req(bias, "vae_conv3d_padded.bias")
-    if resid is not None:
-        _req(resid, "vae_conv3d_padded.resid")
-        if resid.dim() != 2 or resid.shape[0] != T * H * W or resid.stride(1) != 1:
-            raise GoalForceError("vae_conv3d_padded.resid must be [T*H*W, >= N] with contiguous rows")
-        ldr = resid.stride(0)
-    prof = PROFILE_CONV
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    _lib.check(_lib.load().gf_conv3d_padded_bf16(_ptr(buf), _ptr(w), w.stride(0), _ptr(bias), _ptr(out), out.stride(0), T, H, W, C, n, kt,
-                                                 EPI_BIAS if resid is None else EPI_BIAS_RESID, _ptr(resid), ldr, _stream(buf)),
-               "gf_conv3d_padded_bf16")
-    if prof is not None:
-        e1.record()
-        prof.append((e0, e1, T * H * W, n, C, kt, 3, 3, resid is not None))      # mode 3 = the padded-layout direct kernel
+    out = _out(out, "vae_conv3d_padded.out", T * H * W, n, buf.device)
+    ldr = _conv_resid("vae_conv3d_padded", T * H * W, bias, resid)
+    with _timed(PROFILE_CONV, T * H * W, n, C, kt, 3, 3, resid is not None):      # mode 3 = the padded-layout direct kernel
+        _lib.check(_lib.load().gf_conv3d_padded_bf16(_ptr(buf), _ptr(w), w.stride(0), _ptr(bias), _ptr(out), out.stride(0), T, H, W, C, n,
+                                                     kt, EPI_BIAS if resid is None else EPI_BIAS_RESID, _ptr(resid), ldr, _stream(buf)),
+                   "gf_conv3d_padded_bf16")
     return out
 
 
 def vae_finish_latent(x, mean, inv_std, C):
     """x [rows, >=C] (conv1 output, channels-last) -> [rows, C] normalised mu."""
-    _req(x, "vae_finish_latent.x")
-    if x.dim() != 2 or x.stride(1) != 1:
-        raise GoalForceError("vae_finish_latent.x must be 2-D with contiguous rows")
+    _mat(x, "vae_finish_latent.x")
     out = torch.empty((x.shape[0], C), dtype=_BF16, device=x.device)
     _lib.check(_lib.load().gf_vae_finish_latent(_ptr(x), x.stride(0), _ptr(mean), _ptr(inv_std), _ptr(out), x.shape[0], C,
                                                 _stream(x)), "gf_vae_finish_latent")
@@ -918,14 +909,12 @@ def vae_rmsnorm_silu(x, gamma, silu=True, out=None):
 
 def softmax_rows(x, scale, ldo, bias=None, nvalid=None):
     """out[r,:] = softmax(bf16(x[r,:]*scale + bias[r,:])) over the first nvalid columns; zero-padded to ldo columns."""
-    _req(x, "softmax_rows.x")
-    if x.dim() != 2 or x.stride(1) != 1:
-        raise GoalForceError("softmax_rows.x must be 2-D with contiguous rows")
+    _mat(x, "softmax_rows.x")
     ldb = 0
     if bias is not None:
-        _req(bias, "softmax_rows.bias")
-        if bias.shape != x.shape or bias.stride(1) != 1:
-            raise GoalForceError("softmax_rows.bias must match x with contiguous rows")
+        _mat(bias, "softmax_rows.bias")
+        if bias.shape != x.shape:
+            raise GoalForceError("softmax_rows.bias must match x")
         ldb = bias.stride(0)
     out = torch.empty((x.shape[0], ldo), dtype=_BF16, device=x.device)
     _lib.check(_lib.load().gf_softmax_rows(_ptr(x), x.stride(0), _ptr(bias), ldb, _ptr(out), ldo, x.shape[0], x.shape[1],
@@ -937,19 +926,17 @@ def softmax_rows(x, scale, ldo, bias=None, nvalid=None):
 def rowmax_neg(x, out_col):
     """out_col[r] = -max_c x[r, c] (bf16, exact): x [R, C] with contiguous rows, out_col a [R] VIEW (any stride) — a column of the
     augmented Q operand of the VAE attention's second score GEMM (gf_rowmax_neg_bf16)."""
-    _req(x, "rowmax_neg.x")
+    _mat(x, "rowmax_neg.x")
     _req(out_col, "rowmax_neg.out_col")
-    if x.dim() != 2 or x.stride(1) != 1 or out_col.dim() != 1 or out_col.shape[0] != x.shape[0]:
-        raise GoalForceError("rowmax_neg: x [R, C] with contiguous rows, out_col [R]")
+    if out_col.dim() != 1 or out_col.shape[0] != x.shape[0]:
+        raise GoalForceError(f"rowmax_neg.out_col: expected [{x.shape[0]}]")
     _lib.check(_lib.load().gf_rowmax_neg_bf16(_ptr(x), x.stride(0), _ptr(out_col), out_col.stride(0) if out_col.shape[0] > 1 else 1,
                                               x.shape[0], x.shape[1], _stream(x)), "gf_rowmax_neg_bf16")
     return out_col
 
 
 def transpose_pad(x, rpad):
-    _req(x, "transpose_pad.x")
-    if x.dim() != 2 or x.stride(1) != 1:
-        raise GoalForceError("transpose_pad.x must be 2-D with contiguous rows")
+    _mat(x, "transpose_pad.x")
     R, C = x.shape
     out = torch.empty((C, rpad), dtype=_BF16, device=x.device)
     _lib.check(_lib.load().gf_transpose_pad(_ptr(x), x.stride(0), _ptr(out), R, C, rpad, _stream(x)), "gf_transpose_pad")
@@ -1012,7 +999,6 @@ def vae_tile_finalize(values, weight, clamp=True):
 
 
 # ---------------------------------------------------------------------------------- fp8 Linear (VRAM:115-151)
-_FP8 = torch.float8_e4m3fn
 
 
 def quant_fp8_rowscale(x):
@@ -1037,11 +1023,10 @@ def layernorm_modulate_fp8(x, weight=None, bias=None, scale1p=None, shift=None, 
     xv, rows, dim, xs = _rows2d(x, "layernorm_modulate_fp8.x")
     if dim not in LN_FP8_WIDTHS:
         return quant_fp8_rowscale(layernorm_modulate(x, weight=weight, bias=bias, scale1p=scale1p, shift=shift, eps=eps))
-    for n, t in (("weight", weight), ("bias", bias), ("scale1p", scale1p), ("shift", shift)):
-        if t is not None:
-            _req(t, f"layernorm_modulate_fp8.{n}")
-            if t.numel() != dim or not t.is_contiguous():
-                raise GoalForceError(f"layernorm_modulate_fp8.{n}: expected contiguous [{dim}]")
+    _vec(weight, "layernorm_modulate_fp8.weight", dim)
+    _vec(bias, "layernorm_modulate_fp8.bias", dim)
+    _vec(scale1p, "layernorm_modulate_fp8.scale1p", dim)
+    _vec(shift, "layernorm_modulate_fp8.shift", dim)
     out = torch.empty((rows, dim), dtype=_FP8, device=x.device)
     scale = torch.empty((rows,), dtype=torch.float32, device=x.device)
     _lib.check(_lib.load().gf_layernorm_modulate_fp8(_ptr(xv), _ptr(out), _ptr(scale), _ptr(weight), _ptr(bias), _ptr(scale1p),
@@ -1062,42 +1047,9 @@ def cast_fp8(w):
 
 def gemm_fp8(a8, row_scale, w8, bias=None, epilogue=EPI_BIAS, resid=None, gate=None, out=None):
     """out[M,N] = epilogue((a8 @ w8^T) * row_scale[:,None] + bias) — gf_gemm_fp8."""
-    _req(a8, "gemm_fp8.a8", _FP8)
-    _req(w8, "gemm_fp8.w8", _FP8)
-    _req(row_scale, "gemm_fp8.row_scale", torch.float32)
-    if a8.dim() != 2 or w8.dim() != 2 or a8.stride(1) != 1 or w8.stride(1) != 1 or a8.shape[1] != w8.shape[1]:
-        raise GoalForceError("gemm_fp8: a8 [M,K], w8 [N,K] with contiguous rows expected")
-    M, K = a8.shape
-    N = w8.shape[0]
-    if row_scale.numel() != M or not row_scale.is_contiguous():
-        raise GoalForceError("gemm_fp8.row_scale: contiguous [M] expected")
-    if out is None:
-        out = torch.empty((M, N), dtype=_BF16, device=a8.device)
-    ov, Mo, No, ldc = _rows2d(out, "gemm_fp8.out")
-    if (Mo, No) != (M, N):
-        raise GoalForceError("gemm_fp8.out: shape mismatch")
-    ldr = 0
-    if resid is not None:
-        _req(resid, "gemm_fp8.resid")
-        resid, Mr, Nr, ldr = _rows2d(resid, "gemm_fp8.resid")
-        if (Mr, Nr) != (M, N):
-            raise GoalForceError("gemm_fp8.resid: shape mismatch")
-    for n, t in (("gate", gate), ("bias", bias)):
-        if t is not None:
-            _req(t, f"gemm_fp8.{n}")
-            if t.numel() != N or not t.is_contiguous():
-                raise GoalForceError(f"gemm_fp8.{n}: expected contiguous [{N}]")
-    prof = PROFILE_GEMM
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    _lib.check(_lib.load().gf_gemm_fp8(_ptr(a8), a8.stride(0), _ptr(w8), w8.stride(0), _ptr(row_scale), _ptr(bias),
-                                       _ptr(ov), ldc, M, N, K, int(epilogue), _ptr(resid), ldr, _ptr(gate), _stream(a8)),
-               "gf_gemm_fp8")
-    if prof is not None:
-        e1.record()
-        prof.append((e0, e1, M, N, K, int(epilogue)))
-    return out
+    if row_scale is None:
+        raise GoalForceError("gemm_fp8.row_scale: required")
+    return _gemm(a8, w8, row_scale, bias, epilogue, resid, gate, out)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -1159,36 +1111,26 @@ def colsum(a, b=None, gate=None, acc=None):
 
 
 def act_bwd(u, df, kind: str):
-    _req(u, "act_bwd.u")
-    _req(df, "act_bwd.df")
-    if not u.is_contiguous() or not df.is_contiguous() or u.numel() != df.numel():
-        raise GoalForceError("act_bwd: u/df must be contiguous and equal-sized")
+    n = _flat("act_bwd", u=u, df=df)
     du = torch.empty_like(u)
-    _lib.check(_lib.load().gf_act_bwd(_ptr(u), _ptr(df), _ptr(du), u.numel(), {"gelu_tanh": 0, "silu": 1}[kind], _stream(u)),
-               "gf_act_bwd")
+    _lib.check(_lib.load().gf_act_bwd(_ptr(u), _ptr(df), _ptr(du), n, {"gelu_tanh": 0, "silu": 1}[kind], _stream(u)), "gf_act_bwd")
     return du
 
 
 def mse_loss(pred, target, weight=1.0, want_grad=True):
     """(loss fp32 [1] = weight*mean((pred-target)^2), dpred bf16 or None)."""
-    _req(pred, "mse_loss.pred")
-    _req(target, "mse_loss.target")
-    if not pred.is_contiguous() or not target.is_contiguous() or pred.numel() != target.numel():
-        raise GoalForceError("mse_loss: pred/target must be contiguous and equal-sized")
+    n = _flat("mse_loss", pred=pred, target=target)
     loss = torch.empty((1,), dtype=torch.float32, device=pred.device)
     dpred = torch.empty_like(pred) if want_grad else None
     _lib.check(_lib.load().gf_mse_loss(_ptr(pred), _ptr(target), None if dpred is None else _ptr(dpred), _ptr(loss),
-                                       pred.numel(), float(weight), _stream(pred)), "gf_mse_loss")
+                                       n, float(weight), _stream(pred)), "gf_mse_loss")
     return loss, dpred
 
 
 def adamw_step(param, grad, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0):
-    _req(param, "adamw_step.param")
-    _req(grad, "adamw_step.grad")
-    if not param.is_contiguous() or not grad.is_contiguous() or grad.numel() != param.numel():
-        raise GoalForceError("adamw_step: param/grad must be contiguous and equal-sized")
+    n = _flat("adamw_step", param=param, grad=grad)
     _lib.check(_lib.load().gf_adamw_step(_ptr(param), _ptr(grad), _ptr(_f32(exp_avg, "exp_avg")),
-                                         _ptr(_f32(exp_avg_sq, "exp_avg_sq")), param.numel(), float(lr), float(betas[0]),
+                                         _ptr(_f32(exp_avg_sq, "exp_avg_sq")), n, float(lr), float(betas[0]),
                                          float(betas[1]), float(eps), float(weight_decay), int(step), float(grad_scale),
                                          _stream(param)), "gf_adamw_step")
     # the kernel wrote through the raw pointer: tell torch, so that everything derived from the old values (K-padded
@@ -1205,7 +1147,4 @@ def f32_to_bf16(acc):
 
 def sumsq(x, acc):
     """acc[0] += sum(x^2) over a contiguous bf16 tensor (fp32 accumulate)."""
-    _req(x, "sumsq.x")
-    if not x.is_contiguous():
-        raise GoalForceError("sumsq.x must be contiguous")
-    _lib.check(_lib.load().gf_sumsq(_ptr(x), x.numel(), _ptr(_f32(acc, "sumsq.acc")), _stream(x)), "gf_sumsq")
+    _lib.check(_lib.load().gf_sumsq(_ptr(x), _flat("sumsq", x=x), _ptr(_f32(acc, "sumsq.acc")), _stream(x)), "gf_sumsq")

@@ -47,7 +47,11 @@ typedef enum {
 /* library identity ------------------------------------------------------- */
 GF_API const char* gf_version(void);      /* "goalforce-hip <semver> gfx950" */
 GF_API const char* gf_last_error(void);   /* thread-local message of the last failure */
-GF_API int gf_abi_version(void);          /* bumped on any signature change */
+/* The C ABI revision: the ONE number bumped on any signature change, and on any change of what an entry point expects of a
+ * caller-owned buffer under an unchanged signature.  gf_abi_version() returns it; the Python bindings read this line and refuse
+ * a library built from another revision. */
+#define GF_ABI_VERSION 20
+GF_API int gf_abi_version(void);          /* GF_ABI_VERSION of the build */
 /* Dispatch overrides.  Every kernel in the library ships, each for the shapes its launcher sends it; the parity tests cross-check
  * two kernels on the same operands, which needs a way to route a shape to the one that would not get it by default.  Names:
  * "prefer_8wave" (0/1), "a4_stagger" (>= 0), "a4_group_m" (0 = by K), "conv_nb" (0 = by Cout, 1, 2), "conv_gather" (0/1),

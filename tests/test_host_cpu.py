@@ -235,12 +235,67 @@ def test_bindings_refuse_a_library_of_another_abi_revision(monkeypatch):
     overrun through gf_flash_attn_bwd's caller-owned workspace, whose size changed under an unchanged signature)."""
     from goal_force_amd import _lib
     assert _lib.load().gf_abi_version() == _lib.ABI_VERSION
-    src = open(os.path.join(ROOT, "goal_force_amd", "csrc", "gf_abi.hip")).read()
+    src = open(os.path.join(ROOT, "include", "goalforce.h")).read()
     assert int(re.search(r"#define GF_ABI_VERSION (\d+)", src).group(1)) == _lib.ABI_VERSION
+    assert "#define GF_ABI_VERSION" not in open(os.path.join(ROOT, "goal_force_amd", "csrc", "gf_abi.hip")).read()   # one place only
     monkeypatch.setattr(_lib, "_lib", None)
     monkeypatch.setattr(_lib, "ABI_VERSION", _lib.ABI_VERSION + 1)
     with pytest.raises(_lib.GoalForceError, match="ABI revision"):
         _lib.load()
+
+
+def test_bindings_are_read_from_the_header():
+    """_lib derives every restype / argtypes from include/goalforce.h; the awkward entry points, written out."""
+    from ctypes import c_char_p as s, c_float as f, c_int as i, c_int64 as q, c_uint32 as u, c_void_p as p
+    from goal_force_amd import _lib
+    b = _lib.BINDINGS
+    assert _lib.SYMBOLS == tuple(b) and sorted(b) == _header_symbols()
+    assert b["gf_version"] == (s, []) and b["gf_last_error"] == (s, []) and b["gf_abi_version"] == (i, [])
+    assert b["gf_reset_options"] == (None, [])
+    assert b["gf_set_option"] == (i, [s, i]) and b["gf_get_option"] == (i, [s, p])
+    assert b["gf_modulation"] == (i, [p, p, p, q, q, q, u, p])
+    assert b["gf_sage_workspace_bytes"] == (q, [q, q, q]) and b["gf_flash_attn_bwd_workspace_bytes"] == (q, [q, q, q])
+    assert b["gf_conv3d_bf16"] == (i, [p, p, p, q, p, p, q, q, q, q, q, q, i, i, i, i, i, q, q, i, p, q, p])
+    assert b["gf_flash_attn_bwd"] == (i, [p] * 10 + [q] * 12 + [f, p])
+    assert b["gf_adamw_step"] == (i, [p, p, p, p, q, f, f, f, f, f, q, f, p])
+    assert b["gf_canny_u8"] == (i, [p, p, p, p, p, q, q, q, i, i, i, p])
+
+
+def test_header_parser_fails_closed():
+    """A type outside the map, or a GF_API line that is no complete declaration, is refused — never guessed."""
+    from goal_force_amd import _lib
+    ok = "/* c */ GF_API int gf_a(const void* x, int64_t n, // tail\n float eps, void* stream);\nGF_API void gf_b(void);"
+    assert _lib.parse_header(ok) == {"gf_a": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p]),
+                                     "gf_b": (None, [])}
+    for bad, what in (("GF_API int gf_a(const void* x, size_t n);", "size_t"),                  # unknown parameter type
+                      ("GF_API double gf_a(const void* x);", "double"),                         # unknown return type
+                      ("GF_API int gf_a(unsigned int n);", "unsigned"),
+                      ("GF_API int gf_a(void** x);", "gf_a"),                                   # only one level of pointer
+                      ("GF_API int gf_a(int64_t);", "int64_t"),                                 # a parameter without a name
+                      ("GF_API int gf_a(const void* x, int64_t n\nGF_API int gf_b(void);", "gf_a"),   # unterminated
+                      ("GF_API int gf_a(const void* x,", "gf_a"),
+                      ("GF_API int gf_a(void); GF_API int gf_a(void);", "twice")):
+        with pytest.raises(_lib.GoalForceError, match=what):
+            _lib.parse_header(bad)
+
+
+def test_header_is_found_beside_the_package(monkeypatch):
+    from goal_force_amd import _lib
+    assert os.path.samefile(_lib.HEADER_PATH, os.path.join(ROOT, "include", "goalforce.h"))
+    monkeypatch.setattr(_lib, "HEADER_PATH", os.path.join(ROOT, "include", "no_such_header.h"))
+    with pytest.raises(_lib.GoalForceError, match="no_such_header.h"):
+        _lib._read_header()
+
+
+def test_loaded_library_carries_the_declared_signatures():
+    from goal_force_amd import _lib
+    lib = _lib.load()
+    for name in _lib.SYMBOLS:
+        restype, argtypes = _lib.BINDINGS[name]
+        fn = getattr(lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
+    with pytest.raises(TypeError):
+        lib.gf_sage_workspace_bytes(1, 2)           # one argument short: refused by ctypes before the call
 
 
 def test_prompt_cleaner_uses_ftfy_when_importable(monkeypatch, capsys):
