@@ -434,8 +434,14 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(const u16* __restrict__ u,
 }
 
 // loss = weight * mean((pred - target)^2) (fp32 accumulate, F.mse_loss on .float()), dpred = weight * 2 (pred - target) / n
+// Two launches on the caller's stream, no atomics: every workgroup leaves its scaled partial sum in mse_part[blockIdx.x], then
+// mse_finish_kernel adds the partials in one fixed order, so the loss has the same bits on every call, with or without dpred.  (One fp32
+// atomicAdd per workgroup onto loss[0] adds up to 1024 partials in arrival order, which changes with the timing.)  mse_part belongs
+// to the library, one per device: calls of gf_mse_loss on ONE device must be ordered (one stream, as the training step issues them).
+constexpr int MSE_MAX_BLOCKS = 1024;
+__device__ float mse_part[MSE_MAX_BLOCKS];
 __global__ __launch_bounds__(256) void mse_kernel(const u16* __restrict__ pred, const u16* __restrict__ target,
-                                                  u16* __restrict__ dpred, float* __restrict__ loss, long n, float weight) {
+                                                  u16* __restrict__ dpred, long n, float weight) {
     __shared__ float red[4];
     float s = 0.f;
     const float k = 2.0f * weight / (float)n;
@@ -445,7 +451,15 @@ __global__ __launch_bounds__(256) void mse_kernel(const u16* __restrict__ pred, 
         if (dpred) dpred[i] = f2bf(k * d);
     }
     const float tot = block_sum<256>(s, red);
-    if (threadIdx.x == 0) atomicAdd(loss, tot * weight / (float)n);
+    if (threadIdx.x == 0) mse_part[blockIdx.x] = tot * weight / (float)n;
+}
+
+__global__ __launch_bounds__(256) void mse_finish_kernel(float* __restrict__ loss, int nparts) {
+    __shared__ float red[4];
+    float s = 0.f;
+    for (int i = threadIdx.x; i < nparts; i += 256) s += mse_part[i];
+    const float tot = block_sum<256>(s, red);
+    if (threadIdx.x == 0) loss[0] = tot;
 }
 
 // torch.optim.AdamW (decoupled weight decay), bf16 parameter, fp32 moments:
@@ -564,14 +578,11 @@ extern "C" GF_API int gf_mse_loss(const void* pred, const void* target, void* dp
                                   void* stream) {
     GF_CHECK_ARG(pred && target && loss, "gf_mse_loss: null pointer");
     GF_CHECK_ARG(n > 0, "gf_mse_loss: empty input");
-    hipError_t e = hipMemsetAsync(loss, 0, sizeof(float), (hipStream_t)stream);
-    if (e != hipSuccess) {
-        gf_set_error("gf_mse_loss: hipMemsetAsync failed: %s", hipGetErrorString(e));
-        return GF_ERR_LAUNCH;
-    }
-    const unsigned blocks = (unsigned)min((long)((n + 255) / 256), 1024L);
+    const unsigned blocks = (unsigned)min((long)((n + 255) / 256), (long)MSE_MAX_BLOCKS);
     hipLaunchKernelGGL(mse_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const u16*)pred, (const u16*)target,
-                       (u16*)dpred, loss, (long)n, weight);
+                       (u16*)dpred, (long)n, weight);
+    GF_CHECK_LAUNCH("gf_mse_loss");
+    hipLaunchKernelGGL(mse_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, loss, (int)blocks);
     GF_CHECK_LAUNCH("gf_mse_loss");
     return GF_OK;
 }

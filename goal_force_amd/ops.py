@@ -1060,34 +1060,58 @@ def _f32(t, name):
     return t
 
 
+def _f32n(t, name, n: int, at_least=False):
+    """An fp32 operand of the backward kernels (column accumulator, RoPE table): contiguous, n elements (or at least n); None passes."""
+    if t is None:
+        return None
+    _f32(t, name)
+    if t.numel() != n and not (at_least and t.numel() > n):
+        raise GoalForceError(f"{name}: expected {'at least ' if at_least else ''}{n} fp32 elements, got {t.numel()}")
+    return t
+
+
+def _rows_like(t, name: str, rows: int, dim: int):
+    """A second [rows, dim] operand of a row kernel (a row stride of its own is fine) -> (tensor, row stride)."""
+    _req(t, name)
+    v, r, d, stride = _rows2d(t, name)
+    if (r, d) != (rows, dim):
+        raise GoalForceError(f"{name}: expected [{rows}, {dim}] like the first operand, got {tuple(t.shape)}")
+    return v, stride
+
+
 def layernorm_bwd(x, dy, g=None, dg_acc=None, db_acc=None, eps=1e-6):
     """dx of LayerNorm with y = xhat*g (+b) (g = affine weight, or 1+scale, or None); fp32 [dim] accumulators optional."""
     _req(x, "layernorm_bwd.x")
-    _req(dy, "layernorm_bwd.dy")
     xv, rows, dim, xs = _rows2d(x, "layernorm_bwd.x")
-    dv, _, _, ds = _rows2d(dy, "layernorm_bwd.dy")
+    dv, ds = _rows_like(dy, "layernorm_bwd.dy", rows, dim)
+    _vec(g, "layernorm_bwd.g", dim)
+    _f32n(dg_acc, "layernorm_bwd.dg_acc", dim)
+    _f32n(db_acc, "layernorm_bwd.db_acc", dim)
     dx = torch.empty((rows, dim), dtype=_BF16, device=x.device)
-    if g is not None:
-        _req(g, "layernorm_bwd.g")
-    _lib.check(_lib.load().gf_layernorm_bwd(_ptr(xv), xs, _ptr(dv), ds, _ptr(g),
-                                            _ptr(dx), dim, None if dg_acc is None else _ptr(_f32(dg_acc, "dg_acc")),
-                                            None if db_acc is None else _ptr(_f32(db_acc, "db_acc")), rows, dim, float(eps),
-                                            _stream(x)), "gf_layernorm_bwd")
+    _lib.check(_lib.load().gf_layernorm_bwd(_ptr(xv), xs, _ptr(dv), ds, _ptr(g), _ptr(dx), dim, _ptr(dg_acc), _ptr(db_acc),
+                                            rows, dim, float(eps), _stream(x)), "gf_layernorm_bwd")
     return dx.view(x.shape)
 
 
 def rmsnorm_rope_bwd(x_pre, dy, weight, cos=None, sin=None, head_dim=128, eps=1e-6, dw_acc=None):
+    """dx of y = rope(x * rsqrt(mean(x^2) + eps) * weight) for the PRE-norm x; cos / sin fp32 [rows, head_dim/2] or both None (no
+    rotation); dw_acc fp32 [dim] optional."""
     _req(x_pre, "rmsnorm_rope_bwd.x")
-    _req(dy, "rmsnorm_rope_bwd.dy")
     xv, rows, dim, xs = _rows2d(x_pre, "rmsnorm_rope_bwd.x")
-    dv, _, _, ds = _rows2d(dy, "rmsnorm_rope_bwd.dy")
+    dv, ds = _rows_like(dy, "rmsnorm_rope_bwd.dy", rows, dim)
+    _vec(weight, "rmsnorm_rope_bwd.weight", dim, required=True)
+    head_dim = int(head_dim)
+    if (cos is None) != (sin is None):
+        raise GoalForceError("rmsnorm_rope_bwd: cos and sin go together")
+    if head_dim <= 0 or head_dim % 8 or dim % head_dim:
+        raise GoalForceError(f"rmsnorm_rope_bwd: dim={dim} head_dim={head_dim} unsupported (head_dim a multiple of 8 that divides dim)")
+    _f32n(cos, "rmsnorm_rope_bwd.cos", rows * (head_dim // 2), at_least=True)
+    _f32n(sin, "rmsnorm_rope_bwd.sin", rows * (head_dim // 2), at_least=True)
+    _f32n(dw_acc, "rmsnorm_rope_bwd.dw_acc", dim)
     dx = torch.empty((rows, dim), dtype=_BF16, device=x_pre.device)
-    _req(weight, "rmsnorm_rope_bwd.weight")
-    _lib.check(_lib.load().gf_rmsnorm_rope_bwd(_ptr(xv), xs, _ptr(dv), ds, _ptr(weight),
-                                               None if cos is None else _ptr(_f32(cos, "cos")),
-                                               None if sin is None else _ptr(_f32(sin, "sin")), _ptr(dx), dim,
-                                               None if dw_acc is None else _ptr(_f32(dw_acc, "dw_acc")), rows, dim,
-                                               int(head_dim), float(eps), _stream(x_pre)), "gf_rmsnorm_rope_bwd")
+    _lib.check(_lib.load().gf_rmsnorm_rope_bwd(_ptr(xv), xs, _ptr(dv), ds, _ptr(weight), _ptr(cos), _ptr(sin), _ptr(dx), dim,
+                                               _ptr(dw_acc), rows, dim, head_dim, float(eps), _stream(x_pre)),
+               "gf_rmsnorm_rope_bwd")
     return dx.view(x_pre.shape)
 
 
@@ -1095,18 +1119,14 @@ def colsum(a, b=None, gate=None, acc=None):
     """acc[n] += sum_r a[r,n]*(b[r,n] or 1); with `gate` also returns bf16(a*gate) (else None)."""
     _req(a, "colsum.a")
     av, rows, cols, lda = _rows2d(a, "colsum.a")
-    ldb, bp = 0, None
-    if b is not None:
-        _req(b, "colsum.b")
-        bv, _, _, ldb = _rows2d(b, "colsum.b")
-        bp = _ptr(bv)
-    out = None
-    if gate is not None:
-        _req(gate, "colsum.gate")
-        out = torch.empty((rows, cols), dtype=_BF16, device=a.device)
-    _lib.check(_lib.load().gf_colsum(_ptr(av), lda, bp, ldb, None if gate is None else _ptr(gate),
-                                     None if out is None else _ptr(out), cols, None if acc is None else _ptr(_f32(acc, "acc")),
-                                     rows, cols, _stream(a)), "gf_colsum")
+    bv, ldb = (None, 0) if b is None else _rows_like(b, "colsum.b", rows, cols)
+    _vec(gate, "colsum.gate", cols)
+    _f32n(acc, "colsum.acc", cols)
+    if gate is None and acc is None:
+        raise GoalForceError("colsum: nothing to compute (neither acc nor gate given)")
+    out = None if gate is None else torch.empty((rows, cols), dtype=_BF16, device=a.device)
+    _lib.check(_lib.load().gf_colsum(_ptr(av), lda, _ptr(bv), ldb, _ptr(gate), _ptr(out), cols, _ptr(acc), rows, cols,
+                                     _stream(a)), "gf_colsum")
     return None if out is None else out.view(a.shape)
 
 

@@ -263,8 +263,57 @@ def case_misc(rnd, g):
     return f"patchify c={c0}+{c1} F={Fr} H={H} W={W}", e + float((up.float() - ref_up.float()).abs().max()), 0.0
 
 
+def case_bwdrows(rnd, g):
+    """The two row backward kernels of gf_backward.hip (wave-per-row without column accumulators up to dim 5120, 16-rows-per-workgroup with
+    them or above) against fp64 autograd through the per-element bound of tests/backward_refs.py: err = the worst element's share of its
+    allowance (and the accumulators' rel-L2 as a share of their bars), bar 1."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import backward_refs as R
+    cg = torch.Generator().manual_seed(rnd.randrange(2 ** 31))
+    rows = rnd.choice([1, 2, 7, 8, 9, 15, 16, 17, 31, 33, 63, 65, 129, 300, rnd.randrange(1, 600)])
+    dim = 8 * rnd.choice([1, 2, 63, 64, 65, 127, 128, 129, 192, 511, 639, 640, 641, 1023, 1024, rnd.randrange(1, 1025)])
+    accs, strided = rnd.random() < 0.5, rnd.random() < 0.5
+    which = rnd.choice(["ln", "rms"])
+
+    def place(t):                                  # contiguous, or a column slice of a wider buffer
+        if not strided:
+            return t.cuda()
+        pad, off = 8 * rnd.choice([1, 3, 8]), 8 * rnd.choice([0, 1])
+        buf = torch.zeros((t.shape[0], t.shape[1] + pad), dtype=BF, device="cuda")
+        buf[:, off:off + t.shape[1]] = t.cuda()
+        return buf[:, off:off + t.shape[1]]
+
+    def acc():
+        return torch.zeros(dim, device="cuda") if accs else None
+
+    def share(a, ref, bar):
+        return R.rel_l2(a.cpu(), ref) / bar
+    if which == "ln":
+        gmode = rnd.choice(["none", "affine", "scale1p"])
+        x, dy, gm = R.row_inputs(rows, dim, cg, gmode)
+        dx_ref, dg_ref, db_ref = R.layernorm_bwd_ref(x, dy, gm)
+        dg, db = acc(), acc()
+        dx = ops.layernorm_bwd(place(x), place(dy), g=None if gm is None else gm.cuda(), dg_acc=dg, db_acc=db)
+        err = R.violations(dx.cpu(), dx_ref, R.row_rms(dx_ref))[1]
+        if accs:
+            err = max(err, share(dg, dg_ref, 2e-3), share(db, db_ref, 1e-5))
+        return f"layernorm_bwd rows={rows} dim={dim} g={gmode} accs={accs} strided={strided}", err, 1.0
+    hd = rnd.choice([d for d in (8, 16, 64, 128) if dim % d == 0])
+    x, dy, w = R.row_inputs(rows, dim, cg, "affine")
+    rope = rnd.random() < 0.7
+    cos, sin = R.rope_table(rows, hd, cg, rnd.choice([1.0, 0.1275])) if rope else (None, None)
+    dx_ref, dw_ref = R.rmsnorm_rope_bwd_ref(x, dy, w, cos, sin, hd)
+    dw = acc()
+    dx = ops.rmsnorm_rope_bwd(place(x), place(dy), w.cuda(), None if cos is None else cos.cuda(), None if sin is None else sin.cuda(), hd,
+                              1e-6, dw_acc=dw)
+    err = R.violations(dx.cpu(), dx_ref, R.row_rms(dx_ref))[1]
+    if accs:
+        err = max(err, share(dw, dw_ref, 2e-3))
+    return f"rmsnorm_rope_bwd rows={rows} dim={dim} head_dim={hd} rope={rope} accs={accs} strided={strided}", err, 1.0
+
+
 CASES = {"gemm": case_gemm, "attn": case_attn, "rows": case_rows, "cfg": case_cfg, "attnbwd": case_attnbwd, "fp8": case_fp8,
-         "batched": case_batched, "misc": case_misc}
+         "batched": case_batched, "misc": case_misc, "bwdrows": case_bwdrows}
 
 
 def main():
