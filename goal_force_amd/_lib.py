@@ -26,7 +26,8 @@ class GoalForceError(RuntimeError):
 
 # ---- the binding is READ from include/goalforce.h, the file the compiler checks every definition against: the symbol list, each
 # entry point's restype / argtypes and the ABI revision have no second copy here.  A new entry point is declared there, defined
-# in csrc, GF_ABI_VERSION is bumped, and ops.py gets its wrapper.  The parser fails closed: a type outside _CTYPES or a GF_API
+# in csrc, and ops.py gets its wrapper; GF_ABI_VERSION is bumped when a signature or a buffer contract changes (a library that only
+# lacks a new symbol is caught by load(), with the rebuild hint).  The parser fails closed: a type outside _CTYPES or a GF_API
 # line it cannot take apart raises GoalForceError at import — ctypes would accept a wrong row and hand a kernel a shifted pointer.
 _CTYPES = {"void": None, "int": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "uint32_t": ctypes.c_uint32}
 _DECL = re.compile(r"\s+([\w\s*]+?)\s*\b(gf_\w+)\s*\(([^()]*)\)\s*;")

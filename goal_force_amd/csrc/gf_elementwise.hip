@@ -75,6 +75,55 @@ __global__ __launch_bounds__(EW_THREADS) void add_kernel(const u16* __restrict__
     }
 }
 
+// out = bf16(a - b): the fp32 difference of two bf16 values, rounded once (TeaCache's residual, GF:1287).  out may alias a or b:
+// every lane reads its 16 bytes of both operands before it writes them, and no pointer is declared restrict.
+__global__ __launch_bounds__(EW_THREADS) void sub_kernel(const u16* a, const u16* b, u16* out, long n) {
+    const long nvec = n >> 3;
+    const long stride = (long)gridDim.x * EW_THREADS;
+    for (long i = (long)blockIdx.x * EW_THREADS + threadIdx.x; i < nvec; i += stride) {
+        const u16x8 x = reinterpret_cast<const u16x8*>(a)[i];
+        const u16x8 y = reinterpret_cast<const u16x8*>(b)[i];
+        u16x8 o;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = f2bf(bf2f(x[j]) - bf2f(y[j]));
+        reinterpret_cast<u16x8*>(out)[i] = o;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 7)) {
+        const long i = (nvec << 3) + threadIdx.x;
+        out[i] = f2bf(bf2f(a[i]) - bf2f(b[i]));
+    }
+}
+
+// sums[0] = sum |bf16(cur - prev)|, sums[1] = sum |prev| in fp32 (TeaCache's relative L1 distance of two t_mod tensors, GF:1272).
+// ONE block, so the order of every addition is fixed by the code: lane l takes the 16-byte vectors l, l + 256, ... in that
+// order into eight accumulators (one per element position: at n = 30720 each sums 15 terms), folds the eight pairwise, then the
+// wave butterfly and the four wave totals in index order.  No atomics, no second launch; the same bits on every call.
+__global__ __launch_bounds__(EW_THREADS) void rel_l1_kernel(const u16* __restrict__ cur, const u16* __restrict__ prev, long nvec,
+                                                            float* __restrict__ sums) {
+    __shared__ float red[EW_THREADS / 64];
+    float d[8], p[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) d[j] = p[j] = 0.f;
+    for (long i = threadIdx.x; i < nvec; i += EW_THREADS) {
+        const u16x8 c = reinterpret_cast<const u16x8*>(cur)[i];
+        const u16x8 q = reinterpret_cast<const u16x8*>(prev)[i];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float pv = bf2f(q[j]);
+            d[j] += fabsf(rbf(bf2f(c[j]) - pv));
+            p[j] += fabsf(pv);
+        }
+    }
+    const float dsum = ((d[0] + d[1]) + (d[2] + d[3])) + ((d[4] + d[5]) + (d[6] + d[7]));
+    const float psum = ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
+    const float dt = block_sum<EW_THREADS>(dsum, red);
+    const float pt = block_sum<EW_THREADS>(psum, red);
+    if (threadIdx.x == 0) {
+        sums[0] = dt;
+        sums[1] = pt;
+    }
+}
+
 // modulate (DIT:64-65) as the reference's eager bf16 graph: t = bf16(1 + scale); y = bf16(x * t); out = bf16(y + shift);
 // scale / shift are [dim] vectors (the reference's [B, 1, D] operands at B = 1).  dim % 8 == 0.
 __global__ __launch_bounds__(EW_THREADS) void modulate_kernel(const u16* __restrict__ x, u16* __restrict__ out,
@@ -277,6 +326,27 @@ extern "C" GF_API int gf_add_bf16(const void* a, const void* b, void* out, int64
     hipLaunchKernelGGL(add_kernel, dim3(ew_grid(n >> 3)), dim3(EW_THREADS), 0, (hipStream_t)stream, (const u16*)a,
                        (const u16*)b, (u16*)out, (long)n);
     GF_CHECK_LAUNCH("gf_add_bf16");
+    return GF_OK;
+}
+
+extern "C" GF_API int gf_sub_bf16(const void* a, const void* b, void* out, int64_t n, void* stream) {
+    GF_CHECK_ARG(a && b && out && n >= 0, "gf_sub_bf16: null pointer or negative n");
+    GF_CHECK_ARG(gf_aligned16(a) && gf_aligned16(b) && gf_aligned16(out), "gf_sub_bf16: 16-byte alignment required");
+    if (n == 0) return GF_OK;
+    hipLaunchKernelGGL(sub_kernel, dim3(ew_grid(n >> 3)), dim3(EW_THREADS), 0, (hipStream_t)stream, (const u16*)a,
+                       (const u16*)b, (u16*)out, (long)n);
+    GF_CHECK_LAUNCH("gf_sub_bf16");
+    return GF_OK;
+}
+
+extern "C" GF_API int gf_rel_l1_bf16(const void* cur, const void* prev, int64_t n, void* sums, void* stream) {
+    GF_CHECK_ARG(cur && prev && sums, "gf_rel_l1_bf16: null pointer");
+    GF_CHECK_ARG(n > 0 && n % 8 == 0, "gf_rel_l1_bf16: n must be a positive multiple of 8, got %lld", (long long)n);
+    GF_CHECK_ARG(gf_aligned16(cur) && gf_aligned16(prev) && (((uintptr_t)sums) & 3u) == 0,
+                 "gf_rel_l1_bf16: 16-byte aligned operands and a 4-byte aligned sums[2] required");
+    hipLaunchKernelGGL(rel_l1_kernel, dim3(1), dim3(EW_THREADS), 0, (hipStream_t)stream, (const u16*)cur, (const u16*)prev,
+                       (long)(n >> 3), (float*)sums);
+    GF_CHECK_LAUNCH("gf_rel_l1_bf16");
     return GF_OK;
 }
 

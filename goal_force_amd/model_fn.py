@@ -2,7 +2,7 @@
 `pipe.model_fn`, src/goal_force/wan_video_new.py:161, 1349-1591), rebuilt on the HIP kernels.
 
 Same keyword interface as the reference; branches the Goal-Force inference scripts never take
-(S2V, VACE, camera/motion control, TeaCache, sliding window, reference latents, cfg-merged batches)
+(S2V, VACE, camera/motion control, sliding window, reference latents, cfg-merged batches)
 raise NotImplementedError instead of silently doing something else.
 
 Differences that do not change results:
@@ -21,7 +21,11 @@ Differences that do not change results:
   * `cfg_shared` (optional, a dict owned by the caller for ONE denoising step): the cond and the uncond forward of a step differ
     only in the text context, which first enters a block at its cross-attention — the self-attention half of block 0 of the DiT
     and of the ControlNet sees identical inputs in both.  The first forward of the step stores those two tensors in the dict,
-    the second takes them (DiTBlock.forward, `self_attn_memo`): bit-identical results, 2 of 100 self-attentions per step saved.
+    the second takes them (DiTBlock.forward, `self_attn_memo`): bit-identical results, 2 of 100 self-attentions per step saved;
+  * `tea_cache` (teacache.TeaCache, or any object with its `check` / `store` / `update`): on a step the object decides to skip, the
+    reference still runs its ControlNet patch embedding and ControlNet blocks and throws the states away (GF:1489-1522 sit before the
+    branch at GF:1532); here a skipped forward touches neither them nor the `cfg_shared` memo — time embedding, patchify, one add,
+    head, unpatchify.  Under sequence parallelism it is refused: the reference subtracts a chunked x from an unchunked copy there.
 """
 from __future__ import annotations
 
@@ -90,7 +94,7 @@ def model_fn_wan_video(
     **kwargs,
 ):
     for name, val in (("motion_controller", motion_controller), ("vace", vace), ("reference_latents", reference_latents),
-                      ("vace_context", vace_context), ("audio_embeds", audio_embeds), ("tea_cache", tea_cache),
+                      ("vace_context", vace_context), ("audio_embeds", audio_embeds),
                       ("motion_bucket_id", motion_bucket_id), ("sliding_window_size", sliding_window_size),
                       ("control_camera_latents_input", control_camera_latents_input),
                       ("clip_feature", clip_feature if dit.require_clip_embedding else None)):
@@ -101,6 +105,9 @@ def model_fn_wan_video(
         sp = SequenceParallel()          # the reference's flag: Ulysses over the whole world group (GF:1422-1426)
     if sp is not None and sp.size == 1:
         sp = None
+    if tea_cache is not None and sp is not None:
+        raise GoalForceError("model_fn_wan_video: tea_cache with sequence parallelism is not built (the reference's own combination "
+                             "takes the residual of a chunked x against an unchunked copy, GF:1482 / 1531 / 1579)")
     if cfg_merge or latents.shape[0] != 1 or context.shape[0] != 1:
         raise NotImplementedError("cfg_merge / batch > 1: run the cond and uncond forwards separately (GF:710-716)")
     if dit.seperated_timestep and fuse_vae_embedding_in_latents:
@@ -130,6 +137,12 @@ def model_fn_wan_video(
     if sp is not None:                      # GF:1526-1531: contiguous token chunks; RoPE of the chunk (xdit:36-37)
         x = sp.shard_tokens(x).contiguous()
         rope = dit.rope_table_shard(f, h, w, latents.device, sp)
+
+    # TeaCache (GF:1480-1484, 1532-1533): a skipped step replaces everything up to the head by x + the cached residual
+    if tea_cache is not None and tea_cache.check(dit, x, t_mod):
+        x = tea_cache.update(x)
+        x = dit.head(x.unsqueeze(0), t)
+        return dit.unpatchify(x, (f, h, w))
 
     run_cn = use_controlnet and not (elide_zero_controlnet and controlnet.all_zero())
     c = None
@@ -175,6 +188,8 @@ def model_fn_wan_video(
             # x = x + zero_conv(state)   (GF:1565-1570) — Conv1d(k=1) == Linear, fused residual epilogue
             ops.gemm(c, controlnet.zero_conv_weight(block_id), controlnet.controlnet_zero_convs_after[block_id].bias,
                      epilogue=ops.EPI_BIAS_RESID, resid=x, out=x)
+    if tea_cache is not None:
+        tea_cache.store(x)                   # GF:1578-1579
 
     x = dit.head(x.unsqueeze(0), t)          # GF:1581
     if sp is not None:

@@ -16,7 +16,7 @@ from ._lib import (EPI_BIAS, EPI_BIAS_GATE_RESID, EPI_BIAS_GELU_TANH, EPI_BIAS_M
 
 __all__ = [
     "modulation", "layernorm_modulate", "rmsnorm_rope", "gate_residual", "gemm", "flash_attn", "patchify_im2col", "unpatchify",
-    "cfg_euler_step", "act", "add", "force_map",
+    "cfg_euler_step", "act", "add", "sub", "rel_l1", "force_map",
     "EPI_BIAS", "EPI_BIAS_GELU_TANH", "EPI_BIAS_GATE_RESID", "EPI_BIAS_RESID", "EPI_BIAS_SILU", "EPI_BIAS_MUL",
 ]
 
@@ -714,6 +714,28 @@ def add(a, b, out=None):
         out = torch.empty_like(a)
     _lib.check(_lib.load().gf_add_bf16(_ptr(a), _ptr(b), _ptr(out), n, _stream(a)), "gf_add_bf16")
     return out
+
+
+def sub(a, b, out=None):
+    """bf16(a - b), one rounding of the fp32 difference; `out` may be `a` or `b` (TeaCache's residual, teacache.py)."""
+    n = _flat("sub", a=a, b=b, out=out)
+    if out is None:
+        out = torch.empty_like(a)
+    _lib.check(_lib.load().gf_sub_bf16(_ptr(a), _ptr(b), _ptr(out), n, _stream(a)), "gf_sub_bf16")
+    return out
+
+
+def rel_l1(cur, prev):
+    """(sum |bf16(cur - prev)|, sum |prev|) of two equal-sized bf16 tensors as Python floats: one single-block kernel (fp32
+    sums in a fixed order, the same bits on every call) and ONE 8-byte read-back, which waits for the stream — dit.pad_run is
+    the other place the forward does that."""
+    n = _flat("rel_l1", cur=cur, prev=prev)
+    if n == 0 or n % 8:
+        raise GoalForceError(f"rel_l1: the element count must be a positive multiple of 8, got {n}")
+    sums = torch.empty(2, dtype=torch.float32, device=cur.device)
+    _lib.check(_lib.load().gf_rel_l1_bf16(_ptr(cur), _ptr(prev), n, _ptr(sums), _stream(cur)), "gf_rel_l1_bf16")
+    s_diff, s_prev = sums.tolist()
+    return s_diff, s_prev
 
 
 def force_map(frames, H, W, channels, params, centers, clamp01, device):

@@ -26,6 +26,7 @@ from .controlnet import ControlNet
 from .dit import A14B_CONFIG, WanModel
 from .model_fn import ContextCache, model_fn_wan_video
 from .scheduler import FlowMatchScheduler
+from .teacache import TeaCache, coefficients_for  # noqa: F401  (TeaCache: re-exported, it lives beside the pipeline in the reference)
 
 
 class WanVideoPipeline(torch.nn.Module):
@@ -270,13 +271,20 @@ class WanVideoPipeline(torch.nn.Module):
     def denoise(self, latents, context_posi, context_nega, y, control_signal_video_latents, num_inference_steps=50,
                 cfg_scale=5.0, switch_DiT_boundary=0.875, sigma_shift=5.0, denoising_strength=1.0, controlnet=True,
                 progress_bar_cmd=None, record_step_times=False, step_ids=None, cfg_parallel=None,
-                sequence_parallel=None):
+                sequence_parallel=None, tea_cache_l1_thresh=None, tea_cache_model_id=""):
         """GF:663 + GF:697-723.  Returns the final latents [1,16,f,H/8,W/8] (a new tensor).
         `step_ids` (optional) restricts the loop to a sub-range of the schedule (benchmarks).
         `cfg_parallel` (distributed.CfgPairParallel): this rank computes only its branch of the CFG pair and
         exchanges the noise prediction with its partner once per step (RCCL all-gather, 4.2 MB).
         `sequence_parallel` (sequence_parallel.SequenceParallel): every forward runs on this rank's token chunk with
-        head-parallel attention; the noise prediction comes back whole on every rank of the group."""
+        head-parallel attention; the noise prediction comes back whole on every rank of the group.
+        `tea_cache_l1_thresh` / `tea_cache_model_id` (GF:1114-1125): one teacache.TeaCache per CFG branch for this call, shared by
+        both experts; None = off — no object, and the loop is today's.  The decision is a function of the timestep and the expert
+        only, so both ranks of a `cfg_parallel` pair decide alike and each exchanges its prediction either way."""
+        tea_kw = ({}, {})                    # extra keywords of the [cond, uncond] forward
+        if tea_cache_l1_thresh is not None:
+            tea_kw = tuple({"tea_cache": TeaCache(num_inference_steps, rel_l1_thresh=tea_cache_l1_thresh, model_id=tea_cache_model_id)}
+                           for _ in range(2))
         self.scheduler.set_timesteps(num_inference_steps, denoising_strength=denoising_strength, shift=sigma_shift)
         latents = latents.clone()
         models = {"dit": self.dit, "controlnet": self.controlnet if controlnet else None}
@@ -308,7 +316,7 @@ class WanVideoPipeline(torch.nn.Module):
             if cfg_parallel is not None and cfg_scale != 1.0:
                 b = cfg_parallel.branch
                 mine = self.model_fn(**models, **shared, context=context_nega if b else context_posi,
-                                     context_cache=caches[key][b])
+                                     context_cache=caches[key][b], **tea_kw[b])
                 posi, nega = cfg_parallel.exchange(mine)
             else:
                 # both branches on this GPU: the context-independent half of block 0 is computed once (model_fn: cfg_shared)
@@ -321,18 +329,18 @@ class WanVideoPipeline(torch.nn.Module):
                         self._cfg_side_stream = torch.cuda.Stream(self.device)
                     inputs_ready = torch.cuda.Event()
                     inputs_ready.record(main)
-                posi = self.model_fn(**models, **shared, **extra, context=context_posi, context_cache=caches[key][0])
+                posi = self.model_fn(**models, **shared, **extra, context=context_posi, context_cache=caches[key][0], **tea_kw[0])
                 nega = None
                 if two:
                     # enqueued after the whole cond forward (so the events of its block-0 halves exist), running beside it
                     side = self._cfg_side_stream
                     side.wait_event(inputs_ready)
                     with torch.cuda.stream(side):
-                        nega = self.model_fn(**models, **shared, **extra, context=context_nega, context_cache=caches[key][1])
+                        nega = self.model_fn(**models, **shared, **extra, context=context_nega, context_cache=caches[key][1], **tea_kw[1])
                     main.wait_stream(side)
                     nega.record_stream(main)
                 elif cfg_scale != 1.0:
-                    nega = self.model_fn(**models, **shared, **extra, context=context_nega, context_cache=caches[key][1])
+                    nega = self.model_fn(**models, **shared, **extra, context=context_nega, context_cache=caches[key][1], **tea_kw[1])
             sigma, sigma_ = self.scheduler.sigma_pair(self.scheduler.timesteps[progress_id])
             # noise_pred = nega + cfg*(posi - nega); latents += noise_pred*(sigma_next - sigma)  (GF:716, FM:81)
             ops.cfg_euler_step(latents, posi.contiguous(), None if nega is None else nega.contiguous(), cfg_scale,
@@ -367,12 +375,13 @@ class WanVideoPipeline(torch.nn.Module):
                           ("motion_video", motion_video), ("control_video", control_video),
                           ("reference_image", reference_image), ("camera_control_direction", camera_control_direction),
                           ("vace_video", vace_video), ("vace_reference_image", vace_reference_image),
-                          ("motion_bucket_id", motion_bucket_id), ("sliding_window_size", sliding_window_size),
-                          ("tea_cache_l1_thresh", tea_cache_l1_thresh)):
+                          ("motion_bucket_id", motion_bucket_id), ("sliding_window_size", sliding_window_size)):
             if val is not None:
                 raise NotImplementedError(f"`{name}` belongs to a pipeline branch Goal Force never takes (SURVEY §2 #2)")
         if cfg_merge:
             raise NotImplementedError("cfg_merge=True: the reference default (two sequential forwards) is what is built")
+        if tea_cache_l1_thresh is not None:
+            coefficients_for(tea_cache_model_id)       # an unknown id is a ValueError before any work is done (GF:1259-1261)
         height, width, num_frames = self.check_resize_height_width(height, width, num_frames)
         length = (num_frames - 1) // 4 + 1
         noise = self.generate_noise((1, 16, length, height // 8, width // 8), seed=seed, rand_device=rand_device)
@@ -406,7 +415,8 @@ class WanVideoPipeline(torch.nn.Module):
                                switch_DiT_boundary=switch_DiT_boundary, sigma_shift=sigma_shift,
                                denoising_strength=denoising_strength, controlnet=controlnet,
                                progress_bar_cmd=progress_bar_cmd, cfg_parallel=cfg_parallel,
-                               sequence_parallel=sequence_parallel)
+                               sequence_parallel=sequence_parallel, tea_cache_l1_thresh=tea_cache_l1_thresh,
+                               tea_cache_model_id=tea_cache_model_id)
         if output_type == "latent":
             return latents
         if self.vae is None:

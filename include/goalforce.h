@@ -299,6 +299,22 @@ GF_API int gf_act(const void* x, void* out, int64_t n, int kind, void* stream);
 GF_API int gf_add_bf16(const void* a, const void* b, void* out, int64_t n, void* stream);
 
 /* ------------------------------------------------------------------------
+ * TeaCache (GF:1243-1292): the two kernels of the step-skipping cache; its
+ * update on a skipped step is gf_add_bf16.
+ * gf_sub_bf16    — out = bf16(a - b), the fp32 difference rounded once
+ *                  (the residual x_after_blocks - x_patchified, GF:1287).
+ *                  out may alias a or b.
+ * gf_rel_l1_bf16 — sums[0] = sum_i |bf16(cur_i - prev_i)|, sums[1] = sum_i |prev_i|,
+ *                  fp32 accumulation, for the relative L1 distance of two
+ *                  timestep modulations (GF:1272).  One launch of one block,
+ *                  every addition in an order fixed by the code (no atomics):
+ *                  the same bits on every call.  n > 0, n % 8 == 0 (n = 6*dim);
+ *                  sums is fp32[2] on the device, overwritten.
+ */
+GF_API int gf_sub_bf16(const void* a, const void* b, void* out, int64_t n, void* stream);
+GF_API int gf_rel_l1_bf16(const void* cur, const void* prev, int64_t n, void* sums, void* stream);
+
+/* ------------------------------------------------------------------------
  * gf_force_map — renders the Goal-Force control-signal video on the GPU.
  * Replaces the pixel work of ControlSignalDataset_Balls._generate_control_video
  * / get_gaussian_blob / get_blob_for_mass (DS:775-940): every blob contributes
