@@ -48,12 +48,27 @@ __global__ __launch_bounds__(EW_THREADS) void cfg_euler_kernel(u16* __restrict__
     }
 }
 
+// Both activations are v * sigmoid(z).  Far down the negative side 1 + exp(-z) is exp(-z) in fp32 and then overflows to inf, where
+// v / inf = -0 although v * exp(z) is still a normal bf16 number (SiLU for -96 <= v <= -88.7, GELU-tanh for -10.25 <= v <= -10.06):
+// there the result is formed as v * exp(z) with the exponent shifted up, so that only the LAST multiply can leave the normal range
+// (the multiply keeps denormals; the exponential and the reciprocal need not).  Everywhere else the formulas are the ones they always were.
+__device__ __forceinline__ float act_silu(float v) {
+    if (v < -87.0f) return (v * expf(v + 32.0f)) * 1.2664165549094176e-14f;                 // e^-32
+    return v / (1.0f + expf(-v));
+}
+__device__ __forceinline__ float act_gelu_tanh(float v) {
+    const float a = -2.0f * 0.7978845608028654f * 1.4426950408889634f, b = a * 0.044715f;  // gelu_tanh_f's exponent: t = 2^g = exp(-2u)
+    const float g = v * __builtin_fmaf(b, v * v, a);
+    if (g > 100.0f) return (v * __builtin_amdgcn_exp2f(100.0f - g)) * 0x1p-100f;
+    return gelu_tanh_f(v);
+}
+
 template <int KIND>
 __global__ __launch_bounds__(EW_THREADS) void act_kernel(const u16* __restrict__ x, u16* __restrict__ out, long n) {
     const long stride = (long)gridDim.x * EW_THREADS;
     for (long i = (long)blockIdx.x * EW_THREADS + threadIdx.x; i < n; i += stride) {
         const float v = bf2f(x[i]);
-        out[i] = f2bf(KIND == 0 ? v / (1.0f + expf(-v)) : gelu_tanh_f(v));
+        out[i] = f2bf(KIND == 0 ? act_silu(v) : act_gelu_tanh(v));
     }
 }
 

@@ -154,16 +154,16 @@ __global__ __launch_bounds__(64 * WROWS) void layernorm_modulate_wave_kernel(
 #pragma unroll
         for (int j = 0; j < 8; ++j) s += bf2f(v[i][j]);
     }
-    const float mean = wave_sum(s) * (1.0f / DIM);
+    const float mean = wave_sum(s) / (float)DIM;   // correctly rounded (not sum * rounded 1 / DIM): a constant row gives exactly 0
     float q = 0.f;
 #pragma unroll
     for (int i = 0; i < NCH; ++i)
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const float d = bf2f(v[i][j]) - mean;
-            q += d * d;
+            q = __builtin_fmaf(d, d, q);   // written out: left to fp-contract, `q += d * d` may fuse the first two squares either way round
         }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) * (1.0f / DIM) + eps);
+    const float rstd = 1.0f / sqrtf(__builtin_fmaf(wave_sum(q), 1.0f / DIM, eps));
     u16* orow = out + row * out_stride + lane * 8;
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
@@ -198,13 +198,14 @@ __global__ __launch_bounds__(64 * WROWS) void layernorm_modulate_wave_kernel(
 //   MODE 2: modulate(LayerNorm, b, a)      (a = 1 + scale, b = shift: norm1 / norm2 / head, the reference's three bf16 roundings)
 //   FP8: the result is quantised in registers for an fp8_linear consumer (layernorm_modulate_fp8_wave_kernel's contract).
 __device__ __forceinline__ gf_f32x2 unpack2bf(unsigned u) { return gf_f32x2{__uint_as_float(u << 16), __uint_as_float(u & 0xffff0000u)}; }
-__device__ __forceinline__ gf_f32x2 ln2_fma(gf_f32x2 a, gf_f32x2 b, gf_f32x2 c) {
-    return __builtin_elementwise_fma(a, b, c);
-}
 // (contract off: a product must stay a product — the roundings of the reference's separate ops are the point)
 __device__ __forceinline__ gf_f32x2 ln2_mul(gf_f32x2 a, gf_f32x2 b) {
 #pragma clang fp contract(off)
     return a * b;
+}
+__device__ __forceinline__ gf_f32x2 ln2_sub(gf_f32x2 a, gf_f32x2 b) {
+#pragma clang fp contract(off)
+    return a - b;
 }
 __device__ __forceinline__ gf_f32x2 ln2_add(gf_f32x2 a, gf_f32x2 b) {
 #pragma clang fp contract(off)
@@ -233,16 +234,18 @@ __global__ __launch_bounds__(64 * WROWS) void layernorm_wave2_kernel(const u16* 
             s += f[1];
         }
     }
-    // x - mean as ONE fma on the row total, fma(total, -1/DIM, x), and the variance as fma(sum, 1/DIM, eps): what the per-element
-    // kernel's expressions contract to (hipcc's default fp-contract), written out so that both kernels round alike
-    const float tot = wave_sum(s);
-    const gf_f32x2 tot2 = {tot, tot}, ninv2 = {-1.0f / DIM, -1.0f / DIM};
+    // the mean is the correctly rounded total / DIM and x - mean a plain subtraction, as in the per-element kernel: 1 / DIM is not an
+    // fp32 number at 5120 and 1536, and fma(total, -1/DIM, x) left -1.5e-8 x of a CONSTANT row, which rstd = 1/sqrt(eps) turned into
+    // -3.7e-5 where the reference has 0.  The squares are accumulated by fma in element order and the variance is fma(sum, 1/DIM, eps),
+    // written out here and in the per-element kernels so that all of them round alike whatever fp-contract would have chosen
+    const float mean = wave_sum(s) / (float)DIM;
+    const gf_f32x2 mean2 = {mean, mean};
     float q = 0.f;
 #pragma unroll
     for (int i = 0; i < NCH; ++i)
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
-            const gf_f32x2 d = ln2_fma(tot2, ninv2, unpack2bf(v[i][p]));
+            const gf_f32x2 d = ln2_sub(unpack2bf(v[i][p]), mean2);
             q = __builtin_fmaf(d[0], d[0], q);
             q = __builtin_fmaf(d[1], d[1], q);
         }
@@ -260,7 +263,7 @@ __global__ __launch_bounds__(64 * WROWS) void layernorm_wave2_kernel(const u16* 
         u32x4 o;
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
-            gf_f32x2 y = ln2_mul(ln2_fma(tot2, ninv2, unpack2bf(v[i][p])), rstd2);
+            gf_f32x2 y = ln2_mul(ln2_sub(unpack2bf(v[i][p]), mean2), rstd2);
             unsigned r;
             if constexpr (MODE == 1) {
                 y = ln2_add(ln2_mul(y, unpack2bf(a8[p])), unpack2bf(b8[p]));   // * weight, + bias: two roundings, as the per-element kernel
@@ -450,16 +453,16 @@ __global__ __launch_bounds__(64 * WROWS) void layernorm_modulate_fp8_wave_kernel
 #pragma unroll
         for (int j = 0; j < 8; ++j) s += bf2f(v[i][j]);
     }
-    const float mean = wave_sum(s) * (1.0f / DIM);
+    const float mean = wave_sum(s) / (float)DIM;   // correctly rounded (not sum * rounded 1 / DIM): a constant row gives exactly 0
     float q = 0.f;
 #pragma unroll
     for (int i = 0; i < NCH; ++i)
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const float d = bf2f(v[i][j]) - mean;
-            q += d * d;
+            q = __builtin_fmaf(d, d, q);   // written out: left to fp-contract, `q += d * d` may fuse the first two squares either way round
         }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) * (1.0f / DIM) + eps);
+    const float rstd = 1.0f / sqrtf(__builtin_fmaf(wave_sum(q), 1.0f / DIM, eps));
     float mx = 0.f;
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
@@ -502,17 +505,26 @@ __global__ __launch_bounds__(64 * WROWS) void layernorm_modulate_fp8_wave_kernel
     }
 }
 
-// plain bf16 -> e4m3 cast (the weight side of fp8_linear: `weight.to(float8_e4m3fn)`, unit scale, VRAM:138)
+// plain bf16 -> e4m3 cast (the weight side of fp8_linear: `weight.to(float8_e4m3fn)`, unit scale, VRAM:138).  torch rounds to nearest
+// even up to 464 (the tie between 448 and the NaN code rounds down to 448) and gives NaN above, for +-inf and for NaN; whether the
+// conversion instruction saturates or gives NaN there may depend on the wave's overflow mode, so that code is formed here, from the
+// bf16 pattern (464.0 = 0x43E8): sign | 0x7F.
 __global__ __launch_bounds__(256) void cast_fp8_kernel(const u16* __restrict__ x, unsigned char* __restrict__ out, long n8) {
     const long stride = (long)gridDim.x * 256;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n8; i += stride) {
         const u16x8 v = reinterpret_cast<const u16x8*>(x)[i];
-        unsigned w0 = 0, w1 = 0;
-        w0 = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(v[0]), bf2f(v[1]), w0, false);
-        w0 = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(v[2]), bf2f(v[3]), w0, true);
-        w1 = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(v[4]), bf2f(v[5]), w1, false);
-        w1 = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(v[6]), bf2f(v[7]), w1, true);
-        reinterpret_cast<u32x2*>(out)[i] = u32x2{w0, w1};
+        unsigned w[2] = {0, 0};
+        w[0] = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(v[0]), bf2f(v[1]), w[0], false);
+        w[0] = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(v[2]), bf2f(v[3]), w[0], true);
+        w[1] = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(v[4]), bf2f(v[5]), w[1], false);
+        w[1] = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(v[6]), bf2f(v[7]), w[1], true);
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if ((v[j] & 0x7fffu) > 0x43E8u) {
+                const int sh = (j & 3) * 8;
+                w[j >> 2] = (w[j >> 2] & ~(0xffu << sh)) | ((((unsigned)v[j] >> 8 & 0x80u) | 0x7fu) << sh);
+            }
+        reinterpret_cast<u32x2*>(out)[i] = u32x2{w[0], w[1]};
     }
 }
 

@@ -124,6 +124,9 @@ typedef enum {
     GF_EPI_BIAS_MUL = 5        /* bf16(bf16(acc + bias) * resid)  — GEGLU: fc1(x) * gelu(gate(x)),
                                   wan_video_text_encoder.py:106                  */
 } gf_epilogue;
+/* The activations of epilogues 1 and 4 are the plain fp32 formula v / (1 + exp(-z)): in the far negative tail (SiLU for
+ * -96 <= v <= -88.7, GELU-tanh for -10.25 <= v <= -10.06) 1 + exp(-z) overflows and they return -0 where the function is still a
+ * bf16 number (magnitude below 3e-37).  gf_act does not (see there); everywhere else the two agree bit for bit. */
 
 GF_API int gf_gemm_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, const void* bias,
                  void* C, int64_t ldc, int64_t M, int64_t N, int64_t K,
@@ -289,6 +292,8 @@ GF_API int gf_cfg_euler_step(void* latents, const void* posi, const void* nega,
 /* ------------------------------------------------------------------------
  * gf_act — elementwise activation bf16 -> bf16 (fp32 math, one rounding):
  * kind 0 = SiLU (DIT:316,320), 1 = GELU-tanh (DIT:311).
+ * Every finite input is within one bf16 value of bf16(the function in fp64), the far negative tail included (where
+ * x / (1 + exp(-z)) alone overflows to -0: SiLU below -88.7, GELU-tanh below -10.06); -inf gives NaN, as torch's does.
  */
 GF_API int gf_act(const void* x, void* out, int64_t n, int kind, void* stream);
 
@@ -479,7 +484,8 @@ GF_API int gf_layernorm_modulate_fp8(const void* x, void* out8, float* scale, co
 GF_API int gf_linear_vt32_fp8(const void* x8, int64_t ldx, const float* x_scale, const void* w8, int64_t ldw, const void* bias,
                               void* vt, int64_t kv_len, int64_t kv_pad, int64_t N, int64_t K, void* stream);
 
-/* gf_cast_fp8 — bf16 -> e4m3 elementwise (weight.to(float8_e4m3fn), VRAM:138); n % 8 == 0. */
+/* gf_cast_fp8 — bf16 -> e4m3 elementwise (weight.to(float8_e4m3fn), VRAM:138); n % 8 == 0.  torch's codes on every input: round to
+ * nearest even, |x| <= 464 -> at most 448, |x| > 464, +-inf and NaN -> the NaN code (sign | 0x7F): no saturation. */
 GF_API int gf_cast_fp8(const void* x, void* out8, int64_t n, void* stream);
 
 /* gf_gemm_fp8 — C = epilogue((A8 · W8^T) * row_scale[m] + bias); A8 [M,K], W8 [N,K] e4m3 bytes (K contiguous),

@@ -2,6 +2,9 @@
 # Re-creates tools/patches/*_experiments.patch: each is `diff -u <product file> <the same file in the round-4 tree (commit 84a39fb)>`, i.e.
 # applying it to the product file gives back the round-4 file with every experimental kernel / diagnostic branch / env selector in it.
 # Run after any edit to one of these product files (needs the git history; the GPU box never runs this).
+# The diff is of the WHOLE file, so the experimental tree also undoes every later fix to these files: its gf_rowops.hip has the old
+# LayerNorm mean (fma with a rounded 1 / DIM, the sum of squares left to fp-contract) and the old gf_cast_fp8, its goalforce.h lacks the
+# declarations added since.  It is for timing old variants, not for parity.
 set -e
 cd "$(dirname "$0")/../.."
 R4=84a39fb
