@@ -49,6 +49,11 @@ struct AttnArgs {
     long kv_pad;
     float last_key_bias;   // kernel 2 (gf_flash_attn_fwd_lastmult): added to the RAW scores of key kv_len - 1 = log2(multiplicity) / (scale log2 e):
                            // that key then counts `multiplicity` times in the softmax — a run of identical trailing keys folded into one
+    // kernel 3, sparse instantiation only (gf_flash_attn_fwd_vt32_sparse): the key tiles every query block visits, CSR
+    const int* row_ptr;    // [n_maps * n_qblocks + 1]
+    const int* tile_idx;   // ascending inside a row
+    const int* head_map;   // [heads] or NULL (every head: map 0)
+    int n_maps;
 };
 
 // ================================================================================================================
@@ -578,7 +583,23 @@ __device__ __forceinline__ void mfma16(f32x4& acc, const bf16x8& a, const bf16x8
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
 }
 
-template <int NQ>
+// SPARSE (gf_flash_attn_fwd_vt32_sparse): the same pipeline over a LIST of key tiles per query block instead of all of them.
+// The phases count list positions j = 0 .. cnt - 1; position j stands for tile t_j, which enters only the staging addresses and
+// the ragged mask.  "First" (the tile that sets the running maximum) is position 0, whatever its tile; the ragged tile
+// ceil(kv_len / 64) - 1 can only be the last entry of an ascending list, so the steady phases stay mask-free.  A position past
+// the list (the steady phase's K prefetch two ahead) is the empty tile ceil(kv_len / 64), as tile nt is for the dense kernel.
+// Every index read from the map is clamped to [0, ceil(kv_len / 64)] for K (whose descriptor ends with the key sequence) and to
+// one less for V^T (whose descriptor does not), head_map entries to the maps that exist: bad tile numbers give wrong results, never a
+// read outside k / vt.  row_ptr is NOT bounded (the kernel does not know the length of tile_idx): a corrupt row_ptr reads outside the
+// map arrays themselves.
+// The indices are wave-uniform scalar loads from the constant address space.  Three of them (positions p, p + 1, p + 2) sit in
+// SGPRs during phase p and the load of position p + 4 is issued before the phase's closing wait and barrier and taken a whole
+// phase later.  The intent is that no staging slot waits for scalar memory; in the generated code the load does sit right before
+// that wait, but whether its lgkmcnt wait ever holds up the LDS fragment reads has not been measured.  (One index per phase, not a
+// wider chunk: a multi-dword load would read past the end of the last list.)
+// The dense instantiation compiles to the instruction stream it had before the flag existed (every sparse line hangs on the
+// compile-time flag; DESIGN §4.1c has the comparison).
+template <int NQ, bool SPARSE>
 __global__ __launch_bounds__(At3<NQ>::THREADS, (NQ == 2 ? 2 : 1)) void flash_attn_fwd_kernel3(const AttnArgs p) {
     constexpr int NP = At3<NQ>::PIECES, NW = At3<NQ>::WAVES, RW = At3<NQ>::ROWS, NS = At3<NQ>::SLOTS;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -602,6 +623,7 @@ __global__ __launch_bounds__(At3<NQ>::THREADS, (NQ == 2 ? 2 : 1)) void flash_att
     }
     const int q0 = qb0 * QB + wave * RW;
 
+    int vt_last = 0;     // sparse: the last V^T tile that exists (set with the list below)
     bf16x8 qf[NQ][4];   // [qb][ks]: Q[q0 + 16 qb + r][32 ks + 8 g .. +8)
 #pragma unroll
     for (int qb = 0; qb < NQ; ++qb) {
@@ -670,9 +692,10 @@ __global__ __launch_bounds__(At3<NQ>::THREADS, (NQ == 2 ? 2 : 1)) void flash_att
     // which = 0: K tile t -> K buffer buf;  which = 1: V^T tile t -> V buffer buf;  jj = which of the wave's NP pieces
     auto stage_piece = [&](int which, int t, int buf, int jj) __attribute__((always_inline)) {
         GF_LDS char* base = lds + which * AT3_V_BASE + buf * KV_TILE_BYTES + (NW * jj + wave) * 1024;
-        if (which)
+        if (which) {
+            if constexpr (SPARSE) t = min(t, vt_last);     // (the V^T descriptor is unbounded: a tile that exists, whatever the map says)
             dma16b(srd_v, vt_off0, (unsigned)t * (KVB * 2u) + (unsigned)jj * vt_piece, base);
-        else
+        } else
             dma16b(srd_k_tile(t), k_off0, (unsigned)jj * k_piece, base);
     };
     auto stage = [&](int which, int t, int buf) __attribute__((always_inline)) {
@@ -713,7 +736,33 @@ __global__ __launch_bounds__(At3<NQ>::THREADS, (NQ == 2 ? 2 : 1)) void flash_att
 #pragma unroll
         for (int e = 0; e < 8; ++e) ones[e] = o1;
     }
-    const int nt = (p.kv_len + KVB - 1) / KVB;
+    // sparse: this workgroup's list [tl, tl + cnt) and its first five entries (tile_raw: the empty tile past the list; tile_clamp)
+    typedef const __attribute__((address_space(4))) int* cint_p;
+    const int nt_all = (p.kv_len + KVB - 1) / KVB;            // tiles of the key sequence
+    int cnt = 0;
+    cint_p tl = nullptr;
+    auto tile_raw = [&](int j) __attribute__((always_inline)) {
+        int t = nt_all;
+        if (j < cnt) t = tl[j];
+        return t;
+    };
+    auto tile_clamp = [&](int t) __attribute__((always_inline)) { return min(max(t, 0), nt_all); };
+    int w0 = 0, w1 = 0, w2 = 0, w_next = 0, t_first = 0;      // w0 .. w2: tiles of positions p, p + 1, p + 2 in phase p
+    if constexpr (SPARSE) {
+        int map = 0;
+        if (p.head_map) map = min(max(((cint_p)p.head_map)[head], 0), p.n_maps - 1);
+        cint_p rp = (cint_p)p.row_ptr + ((long)map * p.n_qblocks + qb0);
+        const int lo = rp[0];
+        cnt = min(rp[1] - lo, nt_all);       // (ascending indices below nt_all: never more of them)
+        tl = (cint_p)p.tile_idx + lo;
+        t_first = tile_clamp(tile_raw(0));
+        w0 = tile_clamp(tile_raw(1));
+        w1 = tile_clamp(tile_raw(2));
+        w2 = tile_clamp(tile_raw(3));
+        w_next = tile_raw(4);
+        vt_last = nt_all - 1;
+    }
+    const int nt = SPARSE ? cnt : nt_all;                // phases: list positions (sparse) or tiles
     const bool ragged = (p.kv_len & (KVB - 1)) != 0;
     typedef std::integral_constant<int, 0> C0;
     typedef std::integral_constant<int, 1> C1;
@@ -802,7 +851,7 @@ __global__ __launch_bounds__(At3<NQ>::THREADS, (NQ == 2 ? 2 : 1)) void flash_att
     };
     auto mask_ragged = [&](auto par_c, int t) __attribute__((always_inline)) {
         constexpr int PAR = decltype(par_c)::value;
-        if (ragged && t == nt - 1) {
+        if (ragged && t == (SPARSE ? nt_all : nt) - 1) {      // (dense: nt itself)
 #pragma unroll
             for (int kb = 0; kb < 4; ++kb)
 #pragma unroll
@@ -813,7 +862,8 @@ __global__ __launch_bounds__(At3<NQ>::THREADS, (NQ == 2 ? 2 : 1)) void flash_att
                     }
         }
     };
-    auto softmax_plain = [&](auto par_c, int t) __attribute__((always_inline)) {
+    // t: the tile (for the ragged mask);  pos: its position in the phase sequence (0: the tile that sets the running maximum)
+    auto softmax_plain = [&](auto par_c, int t, int pos) __attribute__((always_inline)) {
         constexpr int PAR = decltype(par_c)::value;
         mask_ragged(par_c, t);
         float mx[NQ];
@@ -825,7 +875,7 @@ __global__ __launch_bounds__(At3<NQ>::THREADS, (NQ == 2 ? 2 : 1)) void flash_att
 #pragma unroll
                 for (int j = 0; j < 4; ++j) mx[qb] = fmaxf(mx[qb], sc[PAR][kb][qb][j]);
         }
-        new_max(par_c, mx, t == 0);
+        new_max(par_c, mx, pos == 0);
 #pragma unroll
         for (int qb = 0; qb < NQ; ++qb) {
 #pragma unroll
@@ -874,14 +924,14 @@ __global__ __launch_bounds__(At3<NQ>::THREADS, (NQ == 2 ? 2 : 1)) void flash_att
         }
     };
     // staging: the wave's NP V^T pieces of tile p, then its NP K pieces of tile p+2, one every K3_DMAS slots from slot K3_DMA0
-    auto dma_slot = [&](auto s_c, auto par_c, int pidx) __attribute__((always_inline)) {
+    auto dma_slot = [&](auto s_c, auto par_c, int tv, int tk) __attribute__((always_inline)) {
         constexpr int S = decltype(s_c)::value, PAR = decltype(par_c)::value;
         if constexpr (S >= K3_DMA0 && (S - K3_DMA0) % K3_DMAS == 0 && (S - K3_DMA0) / K3_DMAS < 2 * NP) {
             constexpr int i = (S - K3_DMA0) / K3_DMAS;
             if constexpr (i < NP) {
-                stage_piece(1, pidx, PAR, i);
+                stage_piece(1, tv, PAR, i);
             } else {
-                stage_piece(0, pidx + 2, PAR, i - NP);
+                stage_piece(0, tk, PAR, i - NP);
             }
         }
     };
@@ -916,7 +966,7 @@ __global__ __launch_bounds__(At3<NQ>::THREADS, (NQ == 2 ? 2 : 1)) void flash_att
                 for (int qb = 0; qb < NQ; ++qb) mfma_pv(oacc[NDB - 1][qb], ones, pf(S / (8 * NQ), qb));
             }
             if constexpr (S % NQ == 0) frag_load(std::integral_constant<int, S / NQ + RING - 1>{}, par_c);
-            dma_slot(s_c, par_c, pidx);
+            dma_slot(s_c, par_c, SPARSE ? w0 : pidx, SPARSE ? w2 : pidx + 2);
             // scores of S(p): two per three slots from slot 8 NQ on.  P(p) overwrites pf, which PV(p-1) still reads: pf[0][*] until
             // slot 8 NQ - 1, pf[1][*] until slot 16 NQ - 1 — so the scores that land in pf[0] (key blocks 0, 1) come first (slots
             // 8 NQ .. 20 NQ - 1) and those for pf[1] (key blocks 2, 3) from slot 20 NQ on.
@@ -938,13 +988,19 @@ __global__ __launch_bounds__(At3<NQ>::THREADS, (NQ == 2 ? 2 : 1)) void flash_att
             }
             __builtin_amdgcn_sched_barrier(0);
         });
+        if constexpr (SPARSE) {      // the window moves on; position pidx + 4 is requested, for the K slot of the phase after the next
+            w0 = w1;
+            w1 = w2;
+            w2 = tile_clamp(w_next);
+            w_next = tile_raw(pidx + 4);
+        }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
     };
 
     // ---- prologue: K(0), K(1) staged; S(0)
-    stage(0, 0, 0);
-    if (nt > 1) stage(0, 1, 1);
+    stage(0, SPARSE ? t_first : 0, 0);
+    if (nt > 1) stage(0, SPARSE ? w0 : 1, 1);
     // Q <- bf16(Q * scale * log2 e), under the latency of the staging just issued
 #pragma unroll
     for (int qb = 0; qb < NQ; ++qb)
@@ -957,9 +1013,9 @@ __global__ __launch_bounds__(At3<NQ>::THREADS, (NQ == 2 ? 2 : 1)) void flash_att
     qk_plain(C0{});
     __syncthreads();   // every wave has read K(0) before K(2) overwrites its buffer
     // ---- phase 0 (no PV yet): K(2), V(0) in flight; S(1); softmax(0)
-    if (nt > 2) stage(0, 2, 0);
-    stage(1, 0, 0);
-    softmax_plain(C0{}, 0);          // sets the running maximum (tile 0's row maximum) ...
+    if (nt > 2) stage(0, SPARSE ? w1 : 2, 0);
+    stage(1, SPARSE ? t_first : 0, 0);
+    softmax_plain(C0{}, SPARSE ? t_first : 0, 0);          // sets the running maximum (tile 0's row maximum) ...
     if (nt > 1) qk_plain(C1{});      // ... which S(1) already starts from
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -976,14 +1032,15 @@ __global__ __launch_bounds__(At3<NQ>::THREADS, (NQ == 2 ? 2 : 1)) void flash_att
     // ---- last phase p = nt-1 (nt >= 2): V(nt-1) in flight; PV(nt-2); softmax(nt-1)
     if (nt >= 2) {
         const int par = (nt - 1) & 1;
-        stage(1, nt - 1, par);
+        const int t_last = SPARSE ? w0 : nt - 1;         // (the window has moved with the phases: w0 is position nt - 1 here)
+        stage(1, t_last, par);
         apply_pending();
         if (par) {
             pv_plain(C0{});
-            softmax_plain(C1{}, nt - 1);
+            softmax_plain(C1{}, t_last, nt - 1);
         } else {
             pv_plain(C1{});
-            softmax_plain(C0{}, nt - 1);
+            softmax_plain(C0{}, t_last, nt - 1);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
@@ -1219,31 +1276,41 @@ extern "C" GF_API int gf_transpose_v32(const void* v, int64_t v_stride, void* vt
     return GF_OK;
 }
 
-extern "C" GF_API int gf_flash_attn_fwd_vt32(const void* q, const void* k, const void* vt, void* o, float* lse, int64_t q_len,
-                                             int64_t kv_len, int64_t kv_pad, int64_t heads, int64_t head_dim, int64_t q_stride,
-                                             int64_t k_stride, int64_t o_stride, float scale, void* stream) {
-    GF_CHECK_ARG(q && k && vt && o, "gf_flash_attn_fwd_vt32: null pointer");
+// gf_flash_attn_fwd_vt32 (row_ptr NULL: the dense instantiation) and gf_flash_attn_fwd_vt32_sparse: one set of checks, one launch
+static int flash_attn_vt32_impl(const char* fn, const void* q, const void* k, const void* vt, void* o, float* lse, const int32_t* row_ptr,
+                                const int32_t* tile_idx, const int32_t* head_map, int64_t n_maps, int64_t q_len, int64_t kv_len,
+                                int64_t kv_pad, int64_t heads, int64_t head_dim, int64_t q_stride, int64_t k_stride, int64_t o_stride,
+                                float scale, void* stream) {
+    GF_CHECK_ARG(q && k && vt && o, "%s: null pointer", fn);
     if (head_dim != HD) {
-        gf_set_error("gf_flash_attn_fwd_vt32: head_dim=%ld unsupported (kernel is built for 128)", (long)head_dim);
+        gf_set_error("%s: head_dim=%ld unsupported (kernel is built for 128)", fn, (long)head_dim);
         return GF_ERR_UNSUPPORTED;
     }
     GF_CHECK_ARG(q_len >= 0 && kv_len >= 2 * KVB && heads > 0 && q_len < (1 << 30) && kv_len < (1 << 30),
-                 "gf_flash_attn_fwd_vt32: bad lengths q=%ld kv=%ld heads=%ld (kv_len >= 128)", (long)q_len, (long)kv_len, (long)heads);
-    GF_CHECK_ARG(kv_pad >= kv_len && kv_pad % KVB == 0 && heads * HD * kv_pad < (1LL << 31), "gf_flash_attn_fwd_vt32: bad V^T buffer");
+                 "%s: bad lengths q=%ld kv=%ld heads=%ld (kv_len >= 128)", fn, (long)q_len, (long)kv_len, (long)heads);
+    GF_CHECK_ARG(kv_pad >= kv_len && kv_pad % KVB == 0 && heads * HD * kv_pad < (1LL << 31), "%s: bad V^T buffer", fn);
     GF_CHECK_ARG(q_stride % 8 == 0 && k_stride % 8 == 0 && o_stride % 4 == 0 && q_stride >= heads * HD && k_stride >= heads * HD &&
                      o_stride >= heads * HD,
-                 "gf_flash_attn_fwd_vt32: strides must cover heads*128 and be multiples of 8");
-    GF_CHECK_ARG(gf_aligned16(q) && gf_aligned16(k) && gf_aligned16(vt) && gf_aligned16(o),
-                 "gf_flash_attn_fwd_vt32: 16-byte alignment required");
-    GF_CHECK_ARG((kv_len + 64) * k_stride < (1LL << 31), "gf_flash_attn_fwd_vt32: kv_len*stride must stay below 2^31 elements");
+                 "%s: strides must cover heads*128 and be multiples of 8", fn);
+    GF_CHECK_ARG(gf_aligned16(q) && gf_aligned16(k) && gf_aligned16(vt) && gf_aligned16(o), "%s: 16-byte alignment required", fn);
+    GF_CHECK_ARG((kv_len + 64) * k_stride < (1LL << 31), "%s: kv_len*stride must stay below 2^31 elements", fn);
+    const bool sparse = row_ptr != nullptr;
+    const int64_t n_qblocks = (q_len + QB - 1) / QB;
+    if (sparse)
+        GF_CHECK_ARG(n_maps >= 1 && n_maps * n_qblocks < (1LL << 31) - 1, "%s: n_maps=%ld (at least 1; n_maps * query blocks below 2^31)", fn,
+                     (long)n_maps);
     if (q_len == 0) return GF_OK;
     static GfDeviceOnce once;
     hipError_t e = gf_once_per_device(once, [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(flash_attn_fwd_kernel3<K3_NQ>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, AT3_LDS);
+        hipError_t r = hipFuncSetAttribute(reinterpret_cast<const void*>(flash_attn_fwd_kernel3<K3_NQ, false>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, AT3_LDS);
+        if (r == hipSuccess)
+            r = hipFuncSetAttribute(reinterpret_cast<const void*>(flash_attn_fwd_kernel3<K3_NQ, true>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, AT3_LDS);
+        return r;
     });
     if (e != hipSuccess) {
-        gf_set_error("gf_flash_attn_fwd_vt32: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
+        gf_set_error("%s: hipFuncSetAttribute failed: %s", fn, hipGetErrorString(e));
         return GF_ERR_LAUNCH;
     }
     AttnArgs a;
@@ -1254,7 +1321,7 @@ extern "C" GF_API int gf_flash_attn_fwd_vt32(const void* q, const void* k, const
     a.q_len = (int)q_len;
     a.kv_len = (int)kv_len;
     a.heads = (int)heads;
-    a.n_qblocks = (int)((q_len + QB - 1) / QB);
+    a.n_qblocks = (int)n_qblocks;
     a.q_stride = q_stride;
     a.k_stride = k_stride;
     a.v_stride = k_stride;
@@ -1265,8 +1332,32 @@ extern "C" GF_API int gf_flash_attn_fwd_vt32(const void* q, const void* k, const
     a.kv_pad = kv_pad;
     a.dbg = nullptr;
     a.last_key_bias = 0.f;
-    hipLaunchKernelGGL(flash_attn_fwd_kernel3<K3_NQ>, dim3((unsigned)(a.n_qblocks * a.heads)), dim3(At3<K3_NQ>::THREADS), AT3_LDS,
-                       (hipStream_t)stream, a);
-    GF_CHECK_LAUNCH("gf_flash_attn_fwd_vt32");
+    a.row_ptr = row_ptr;
+    a.tile_idx = tile_idx;
+    a.head_map = head_map;
+    a.n_maps = (int)n_maps;
+    const dim3 grid((unsigned)(a.n_qblocks * a.heads)), block(At3<K3_NQ>::THREADS);
+    if (sparse)
+        hipLaunchKernelGGL((flash_attn_fwd_kernel3<K3_NQ, true>), grid, block, AT3_LDS, (hipStream_t)stream, a);
+    else
+        hipLaunchKernelGGL((flash_attn_fwd_kernel3<K3_NQ, false>), grid, block, AT3_LDS, (hipStream_t)stream, a);
+    GF_CHECK_LAUNCH(fn);
     return GF_OK;
+}
+
+extern "C" GF_API int gf_flash_attn_fwd_vt32(const void* q, const void* k, const void* vt, void* o, float* lse, int64_t q_len,
+                                             int64_t kv_len, int64_t kv_pad, int64_t heads, int64_t head_dim, int64_t q_stride,
+                                             int64_t k_stride, int64_t o_stride, float scale, void* stream) {
+    return flash_attn_vt32_impl("gf_flash_attn_fwd_vt32", q, k, vt, o, lse, nullptr, nullptr, nullptr, 0, q_len, kv_len, kv_pad, heads,
+                                head_dim, q_stride, k_stride, o_stride, scale, stream);
+}
+
+extern "C" GF_API int gf_flash_attn_fwd_vt32_sparse(const void* q, const void* k, const void* vt, void* o, float* lse,
+                                                    const int32_t* row_ptr, const int32_t* tile_idx, const int32_t* head_map,
+                                                    int64_t n_maps, int64_t q_len, int64_t kv_len, int64_t kv_pad, int64_t heads,
+                                                    int64_t head_dim, int64_t q_stride, int64_t k_stride, int64_t o_stride, float scale,
+                                                    void* stream) {
+    GF_CHECK_ARG(row_ptr && tile_idx, "gf_flash_attn_fwd_vt32_sparse: null map pointer");
+    return flash_attn_vt32_impl("gf_flash_attn_fwd_vt32_sparse", q, k, vt, o, lse, row_ptr, tile_idx, head_map, n_maps, q_len, kv_len,
+                                kv_pad, heads, head_dim, q_stride, k_stride, o_stride, scale, stream);
 }

@@ -40,8 +40,9 @@ class RopeTable:
     Built once per (f, h, w) grid instead of the reference's per-forward CPU rebuild + H2D copy
     (GF:1474-1478)."""
 
-    def __init__(self, freqs_complex: torch.Tensor, device):
+    def __init__(self, freqs_complex: torch.Tensor, device, grid=None):
         fc = freqs_complex.reshape(freqs_complex.shape[0], -1)
+        self.grid = grid                  # the (f, h, w) token grid when the table was built from one (sparse attention patterns ask for it)
         self.cos = fc.real.to(torch.float32).contiguous().to(device)
         self.sin = fc.imag.to(torch.float32).contiguous().to(device)
         self.tokens = fc.shape[0]
@@ -63,7 +64,7 @@ class RopeTable:
             freqs3[1][:h].view(1, h, 1, -1).expand(f, h, w, -1),
             freqs3[2][:w].view(1, 1, w, -1).expand(f, h, w, -1),
         ], dim=-1).reshape(f * h * w, -1)
-        return RopeTable(tab, device)
+        return RopeTable(tab, device, grid=(f, h, w))
 
 
 def Q_PRESCALE(head_dim: int) -> float:
@@ -213,6 +214,31 @@ def enable_sage_attention(module: nn.Module, enabled=True):
     return module
 
 
+def enable_sparse_attention(module: nn.Module, pattern, dense_blocks: int = 0):
+    """Block-sparse self-attention (sparse_attention.py; the reference has no counterpart): every SelfAttention inside the DiT /
+    ControlNet blocks of `module` (a WanModel, a ControlNet, a block or a whole pipeline) runs ops.flash_attn_sparse on the map
+    `pattern(grid)` of the token grid it is called on — a sparse_attention.FrameWindow, or any callable grid -> ops.BlockMap (the
+    hook for per-head maps).  `dense_blocks` = n keeps the first n blocks of every stack (`.blocks`) on the dense kernel.
+    pattern=None restores the dense path bit for bit.  Inference on one GPU only: a switched block refuses training (`keep`),
+    sequence parallelism, enable_sage_attention, a caller's own `freqs` (no grid) and key counts below ops.VT_MIN_KV by name instead
+    of falling back.  pipe.sparse_dense_steps = n runs the first n sampling steps densely (model_fn_wan_video(sparse_dense=True))."""
+    if pattern is not None and not callable(pattern):
+        raise GoalForceError(f"enable_sparse_attention: expected a callable grid -> ops.BlockMap (or None), got {type(pattern).__name__}")
+    if int(dense_blocks) != dense_blocks or dense_blocks < 0:
+        raise GoalForceError(f"enable_sparse_attention: expected dense_blocks >= 0, got {dense_blocks!r}")
+    in_stack = set()
+    for m in module.modules():
+        if isinstance(getattr(m, "blocks", None), nn.ModuleList):
+            for i, blk in enumerate(m.blocks):
+                if isinstance(blk, DiTBlock):
+                    blk.self_attn._gf_sparse = pattern if i >= dense_blocks else None
+                    in_stack.add(id(blk))
+    for blk in module.modules():
+        if isinstance(blk, DiTBlock) and id(blk) not in in_stack:       # a block handed over on its own
+            blk.self_attn._gf_sparse = pattern
+    return module
+
+
 def sageattn(q, k, v, tensor_layout="HND", is_causal=False, sm_scale=None, return_lse=False, **kw):
     """Drop-in for `sageattention.sageattn` as the reference calls it (DIT:50-54): q, k, v [B, heads, S, 128] ("HND", the strided
     `rearrange(q, "b s (n d) -> b n s d")` views are fine) or [B, S, heads, 128] ("NHD") bf16 -> the same layout, on
@@ -286,18 +312,45 @@ class SelfAttention(nn.Module):
         self.q, self.k, self.v, self.o = (nn.Linear(dim, dim) for _ in range(4))
         self.norm_q, self.norm_k = RMSNorm(dim, eps=eps), RMSNorm(dim, eps=eps)
 
-    def attend(self, x2: torch.Tensor, rope: RopeTable, sp=None, keep=None) -> torch.Tensor:
+    def attend(self, x2: torch.Tensor, rope: RopeTable, sp=None, keep=None, dense=False) -> torch.Tensor:
         """x2 [S,D] -> attention output BEFORE the o projection, [S,D].  With a sequence_parallel.SequenceParallel
         group `sp`, x2 and rope are this rank's token chunk and the heads are exchanged over xGMI (usp_attn_forward,
         diffsynth/distributed/xdit_context_parallel.py:109-131).  `keep` (a dict, training): the attention output and the
         rows' log-sum-exp are stored under "attn" / "lse" so that the backward does not run the attention again; with
-        keep["wide"] also the three projections ("qp", "kp" before their norm, "v")."""
+        keep["wide"] also the three projections ("qp", "kp" before their norm, "v").  `dense`: a block switched by
+        enable_sparse_attention attends densely in this call (pipe.sparse_dense_steps)."""
         fp8 = getattr(self.q, "_gf_w8", None) is not None
         sage = getattr(self, "_gf_sage", False)
         if sage and keep is not None:
             raise GoalForceError("training through a block with enable_sage_attention is refused (the sage backend has no backward): "
                                  "call enable_sage_attention(module, False) first")
         attn = ops.sage_attn if sage else ops.flash_attn
+        pattern = getattr(self, "_gf_sparse", None)
+        if pattern is not None and not dense:
+            # every refusal comes before the first kernel: a switched block never falls back to the dense path on its own
+            if sage:
+                raise GoalForceError("sparse attention with enable_sage_attention is refused (the sage kernel takes no block map): switch one off")
+            if keep is not None:
+                raise GoalForceError("training through a block with enable_sparse_attention is refused (there is no sparse backward): "
+                                     "call enable_sparse_attention(module, None) first")
+            if sp is not None:
+                raise GoalForceError("sparse attention under sequence parallelism is refused (the head-parallel exchange takes no block map)")
+            grid = getattr(rope, "grid", None)
+            if grid is None:
+                raise GoalForceError("sparse attention needs the token grid: expected a RopeTable built by WanModel.rope_table "
+                                     "(RopeTable.from_grid), got rotary phases without one")
+            if x2.shape[0] != grid[0] * grid[1] * grid[2]:
+                raise GoalForceError(f"sparse attention: expected {grid[0] * grid[1] * grid[2]} tokens for the grid {grid}, got {x2.shape[0]}")
+            if x2.shape[0] < ops.VT_MIN_KV:
+                raise GoalForceError(f"sparse attention: expected at least {ops.VT_MIN_KV} tokens (ops.VT_MIN_KV, where the self-attention "
+                                     f"runs on kernel 3), got {x2.shape[0]}")
+            block_map = pattern(grid)
+            if not isinstance(block_map, ops.BlockMap):
+                raise GoalForceError(f"sparse attention: expected the pattern to return an ops.BlockMap, got {type(block_map).__name__}")
+            block_map = block_map.to(rope.cos.device)
+
+            def attn(q, k, v, num_heads, vt=None, scale=None):
+                return ops.flash_attn_sparse(q, k, v, num_heads, block_map, vt=vt, scale=scale)
         xin = (x2 if isinstance(x2, QuantizedInput) else QuantizedInput(x2)) if fp8 else x2
         # Q leaves its RMSNorm + RoPE kernel already multiplied by c = softmax scale x log2(e) (the rotation table carries the factor:
         # RopeTable.scaled), and the attention is called with scale = ln 2, i.e. c = 1 inside — its `Q <- bf16(Q c)` is then exact.
@@ -468,8 +521,9 @@ class DiTBlock(nn.Module):
         self.gate = GateModule()
 
     def forward(self, x, context, t_mod, freqs, context_kv=None, out=None, sp=None, keep=None, self_attn_memo=None,
-                fold_pad_keys=True, pad_n=None):
-        """`self_attn_memo` (a dict, optional): x + gate_msa * self_attn(modulate(norm1(x))) — the block's first half — does not
+                fold_pad_keys=True, pad_n=None, dense_attn=False):
+        """`dense_attn`: SelfAttention.attend's `dense` (a sparse-switched block attends densely in this call).
+        `self_attn_memo` (a dict, optional): x + gate_msa * self_attn(modulate(norm1(x))) — the block's first half — does not
         depend on the text context.  The two forwards of a CFG step run this block on IDENTICAL x, t_mod and freqs (block 0 of the
         DiT and of the ControlNet, model_fn_wan_video), so the first stores that half here and the second takes it: same kernels
         on the same inputs, the same bits, one attention and four projections fewer."""
@@ -495,7 +549,7 @@ class DiTBlock(nn.Module):
                 h = QuantizedInput.layernorm(x2, scale1p=mod[1], shift=mod[0], eps=self.eps)
             else:
                 h = ops.layernorm_modulate(x2, scale1p=mod[1], shift=mod[0], eps=self.eps)          # DIT:225
-            a = self.self_attn.attend(h, rope, sp, keep)
+            a = self.self_attn.attend(h, rope, sp, keep, dense=dense_attn)
             x_new = out if out is not None else torch.empty_like(x2)
             linear(a, self.self_attn.o, epilogue=ops.EPI_BIAS_GATE_RESID, resid=x2, gate=mod[2], out=x_new)   # DIT:226
             if keep is not None and keep.get("wide"):

@@ -26,6 +26,7 @@ Differences that do not change results:
     reference still runs its ControlNet patch embedding and ControlNet blocks and throws the states away (GF:1489-1522 sit before the
     branch at GF:1532); here a skipped forward touches neither them nor the `cfg_shared` memo — time embedding, patchify, one add,
     head, unpatchify.  Under sequence parallelism it is refused: the reference subtracts a chunked x from an unchunked copy there.
+  * `sparse_dense` (pipe.sparse_dense_steps): blocks switched by dit.enable_sparse_attention attend densely in this forward.
 """
 from __future__ import annotations
 
@@ -91,6 +92,7 @@ def model_fn_wan_video(
     elide_zero_controlnet: bool = True,
     sequence_parallel=None,
     cfg_shared: Optional[dict] = None,
+    sparse_dense: bool = False,
     **kwargs,
 ):
     for name, val in (("motion_controller", motion_controller), ("vace", vace), ("reference_latents", reference_latents),
@@ -180,10 +182,10 @@ def model_fn_wan_video(
             cb = controlnet.controlnet_dit.blocks[block_id]
             c = cb(c, ctx, t_mod, rope, context_kv=kv_for(context_cache.cn_kv if context_cache else None,
                                                           context_cache.cn_u if context_cache else None, cb, block_id),
-                   sp=sp, self_attn_memo=memo_cn, pad_n=pad_n)
+                   sp=sp, self_attn_memo=memo_cn, pad_n=pad_n, dense_attn=sparse_dense)
         x = block(x, ctx, t_mod, rope, context_kv=kv_for(context_cache.dit_kv if context_cache else None,
                                                          context_cache.dit_u if context_cache else None, block, block_id),
-                  sp=sp, self_attn_memo=memo_dit, pad_n=pad_n)
+                  sp=sp, self_attn_memo=memo_dit, pad_n=pad_n, dense_attn=sparse_dense)
         if block_id < n_cn:
             # x = x + zero_conv(state)   (GF:1565-1570) — Conv1d(k=1) == Linear, fused residual epilogue
             ops.gemm(c, controlnet.zero_conv_weight(block_id), controlnet.controlnet_zero_convs_after[block_id].bias,

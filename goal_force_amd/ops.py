@@ -15,7 +15,7 @@ from ._lib import (EPI_BIAS, EPI_BIAS_GATE_RESID, EPI_BIAS_GELU_TANH, EPI_BIAS_M
                    GoalForceError)
 
 __all__ = [
-    "modulation", "layernorm_modulate", "rmsnorm_rope", "gate_residual", "gemm", "flash_attn", "patchify_im2col", "unpatchify",
+    "modulation", "layernorm_modulate", "rmsnorm_rope", "gate_residual", "gemm", "flash_attn", "flash_attn_sparse", "BlockMap", "patchify_im2col", "unpatchify",
     "cfg_euler_step", "act", "add", "sub", "rel_l1", "force_map",
     "EPI_BIAS", "EPI_BIAS_GELU_TANH", "EPI_BIAS_GATE_RESID", "EPI_BIAS_RESID", "EPI_BIAS_SILU", "EPI_BIAS_MUL",
 ]
@@ -389,15 +389,20 @@ def linear_vt32_fp8(x8, x_scale, w8, bias):
     return _linear_vt32(x8, w8, x_scale, bias)
 
 
-def _vt_attn(lib, q, k, v, vt, out, lse, sq, skv, num_heads, head_dim, scale, k3):
-    """The attention over a pre-transposed V, shared by flash_attn and flash_attn_lse: kernel 3 (16x16x32 MFMAs), or (k3 False:
-    options(attn_k3=False) for the cross-check tests, a finished q) kernel 2 (32x32x16).  vt None: V^T is made here from v."""
+def _vt_attn(lib, q, k, v, vt, out, lse, sq, skv, num_heads, head_dim, scale, k3, block_map=None):
+    """The attention over a pre-transposed V, shared by flash_attn, flash_attn_lse and flash_attn_sparse: kernel 3 (16x16x32 MFMAs),
+    or (k3 False: options(attn_k3=False) for the cross-check tests, a finished q) kernel 2 (32x32x16).  vt None: V^T is made here
+    from v.  block_map (a BlockMap, kernel 3 only): gf_flash_attn_fwd_vt32_sparse, which takes the map after lse."""
     tr, fa = (lib.gf_transpose_v32, lib.gf_flash_attn_fwd_vt32) if k3 else (lib.gf_transpose_v, lib.gf_flash_attn_fwd_vt)
+    tiles = ()
+    if block_map is not None:
+        fa = lib.gf_flash_attn_fwd_vt32_sparse
+        tiles = (_ptr(block_map.row_ptr), _ptr(block_map.tile_idx), _ptr(block_map.head_map), block_map.n_maps)
     if vt is None:
         vt = _vt_workspace(num_heads * 128 * kv_pad(skv), q.device)
         _lib.check(tr(_ptr(v), v.stride(0), _ptr(vt), skv, kv_pad(skv), num_heads, _stream(q)), "gf_transpose_v")
-    _lib.check(fa(_ptr(q), _ptr(k), _ptr(vt), _ptr(out), _ptr(lse), sq, skv, kv_pad(skv), num_heads, head_dim,
-                  q.stride(0), k.stride(0), out.stride(0), float(scale), _stream(q)), "gf_flash_attn_fwd_vt")
+    _lib.check(fa(_ptr(q), _ptr(k), _ptr(vt), _ptr(out), _ptr(lse), *tiles, sq, skv, kv_pad(skv), num_heads, head_dim,
+                  q.stride(0), k.stride(0), out.stride(0), float(scale), _stream(q)), fa.__name__ if tiles else "gf_flash_attn_fwd_vt")
 
 
 def flash_attn(q, k, v, num_heads, out=None, scale=None, vt=None, last_key_mult=1, finished_q=False):
@@ -444,6 +449,127 @@ def flash_attn(q, k, v, num_heads, out=None, scale=None, vt=None, last_key_mult=
                                              q.stride(0), k.stride(0), v.stride(0), out.stride(0), float(scale),
                                              _stream(q)), "gf_flash_attn_fwd")
     return out
+
+
+# ---- block-sparse self-attention (gf_flash_attn_fwd_vt32_sparse: kernel 3 over a list of key tiles per query block)
+SPARSE_QB, SPARSE_KB = 256, 64              # query rows per map row, keys per map column: kernel 3's workgroup and key tile
+
+
+class BlockMap:
+    """Which 64-key tiles every 256-row query block attends to, as the kernel reads it: CSR (`row_ptr` int32
+    [n_maps * n_qblocks + 1], `tile_idx` int32 ascending inside a row) and an optional `head_map` int32 [heads] (head h uses map
+    head_map[h]; None: every head uses map 0).  Built and validated on the host from a CPU bool array `mask` [n_maps, n_qblocks,
+    n_tiles] (a 2-D array is one map), uploaded once (`device`; None keeps it on the host, `to(device)` uploads a copy).
+    `q_len` / `kv_len`: the (lowest, highest) sequence lengths the map fits; `density`: selected / all (query block, tile) pairs,
+    averaged over the heads when there is a head_map.  The kernel clamps the indices but cannot validate them — this class is
+    where a map is checked: every row selects at least 2 tiles (the validated two-tile pipeline)."""
+
+    def __init__(self, mask, head_map=None, device=None):
+        mask = torch.as_tensor(mask)
+        if mask.is_cuda or mask.dtype != torch.bool:
+            raise GoalForceError(f"BlockMap.mask: expected a CPU bool array, got {mask.dtype} on {mask.device}")
+        if mask.dim() == 2:
+            mask = mask[None]
+        if mask.dim() != 3 or min(mask.shape) < 1:
+            raise GoalForceError(f"BlockMap.mask: expected [n_maps, n_qblocks, n_tiles], got {tuple(mask.shape)}")
+        self.n_maps, self.n_qblocks, self.n_tiles = mask.shape
+        if self.n_tiles < 2:
+            raise GoalForceError(f"BlockMap.mask: expected at least 2 key tiles, got {self.n_tiles}")
+        counts = mask.sum(dim=2).reshape(-1)
+        if int(counts.min()) < 2:
+            m, b = divmod(int(counts.argmin()), self.n_qblocks)
+            raise GoalForceError(f"BlockMap.mask: expected at least 2 tiles in every row, got {int(counts.min())} in map {m}, query block {b}")
+        if head_map is not None:
+            head_map = torch.as_tensor(head_map).to(torch.int64).reshape(-1)
+            if head_map.numel() < 1 or int(head_map.min()) < 0 or int(head_map.max()) >= self.n_maps:
+                raise GoalForceError(f"BlockMap.head_map: expected map numbers in [0, {self.n_maps}), got {head_map.tolist()}")
+            head_map = head_map.to(torch.int32).contiguous()
+        row_ptr = torch.zeros(counts.numel() + 1, dtype=torch.int64)
+        row_ptr[1:] = counts.cumsum(0)
+        self.row_ptr = row_ptr.to(torch.int32)
+        self.tile_idx = mask.reshape(-1, self.n_tiles).nonzero()[:, 1].to(torch.int32).contiguous()     # row-major: ascending per row
+        self.head_map = head_map
+        per_map = counts.reshape(self.n_maps, -1).sum(1).double() / (self.n_qblocks * self.n_tiles)
+        self.density = float(per_map.mean() if head_map is None else per_map[head_map.long()].mean())
+        self.q_len = ((self.n_qblocks - 1) * SPARSE_QB + 1, self.n_qblocks * SPARSE_QB)
+        self.kv_len = ((self.n_tiles - 1) * SPARSE_KB + 1, self.n_tiles * SPARSE_KB)
+        if device is not None:
+            self._upload(torch.device(device))
+
+    def _upload(self, device):
+        self.row_ptr, self.tile_idx = self.row_ptr.to(device), self.tile_idx.to(device)
+        if self.head_map is not None:
+            self.head_map = self.head_map.to(device)
+
+    @property
+    def device(self):
+        return self.row_ptr.device
+
+    def to(self, device):
+        """The map on `device`: itself when it is there already, else a copy made once per device."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if device == self.device:
+            return self
+        copies = self.__dict__.setdefault("_copies", {})        # uploaded once per device
+        if device not in copies:
+            other = object.__new__(BlockMap)
+            other.__dict__.update({k: v for k, v in self.__dict__.items() if k != "_copies"})
+            other._upload(device)
+            copies[device] = other
+        return copies[device]
+
+    def counts(self):
+        """Tiles per row, CPU int64 [n_maps, n_qblocks]."""
+        rp = self.row_ptr.cpu().long()
+        return (rp[1:] - rp[:-1]).reshape(self.n_maps, self.n_qblocks)
+
+    def mask(self):
+        """The bool array the map was built from, rebuilt from the CSR form (CPU)."""
+        rows = torch.repeat_interleave(torch.arange(self.n_maps * self.n_qblocks), self.counts().reshape(-1))
+        m = torch.zeros((self.n_maps * self.n_qblocks, self.n_tiles), dtype=torch.bool)
+        m[rows, self.tile_idx.cpu().long()] = True
+        return m.reshape(self.n_maps, self.n_qblocks, self.n_tiles)
+
+
+def flash_attn_sparse(q, k, v, num_heads, block_map, out=None, scale=None, vt=None, lse=False):
+    """flash_attn restricted to the key tiles of `block_map` (a BlockMap on q's device): query block b of head h takes its softmax
+    over the keys of the tiles the map lists for it and over no others — gf_flash_attn_fwd_vt32_sparse, kernel 3's sparse
+    instantiation.  q [Sq, H*128], k / v [Skv, H*128] bf16 (row-strided views OK), Skv >= 128; `vt` (instead of v): the V^T operand
+    linear_vt32 / linear_vt32_fp8 wrote for these keys.  lse=True: returns (out, log2-domain log-sum-exp [Sq, H] fp32) over the
+    selected keys.  Forward only."""
+    for n, t in (("q", q), ("k", k)) + ((("v", v),) if vt is None else ()):
+        _mat(t, f"flash_attn_sparse.{n}")
+    sq, hd_all = q.shape
+    skv = k.shape[0]
+    if hd_all != num_heads * 128 or k.shape[1] != hd_all or (vt is None and v.shape != k.shape):
+        raise GoalForceError(f"flash_attn_sparse: expected q [Sq, {num_heads}*128] and k / v [Skv, {num_heads}*128], got "
+                             f"{tuple(q.shape)} / {tuple(k.shape)}")
+    if skv < 2 * SPARSE_KB or sq < 1:
+        raise GoalForceError(f"flash_attn_sparse: expected at least 1 query and {2 * SPARSE_KB} keys, got {sq} / {skv}")
+    if num_heads * 128 * kv_pad(skv) >= 2 ** 31:
+        raise GoalForceError("flash_attn_sparse: expected heads*128*kv_pad below 2^31 elements (the V^T operand's indices)")
+    if not isinstance(block_map, BlockMap):
+        raise GoalForceError(f"flash_attn_sparse.block_map: expected an ops.BlockMap, got {type(block_map).__name__}")
+    if block_map.device != q.device:
+        raise GoalForceError(f"flash_attn_sparse.block_map: expected the map on {q.device}, got {block_map.device} (BlockMap.to)")
+    if (block_map.n_qblocks, block_map.n_tiles) != (-(-sq // SPARSE_QB), -(-skv // SPARSE_KB)):
+        raise GoalForceError(f"flash_attn_sparse.block_map: expected [{-(-sq // SPARSE_QB)} query blocks, {-(-skv // SPARSE_KB)} tiles] for "
+                             f"{sq} queries and {skv} keys, got [{block_map.n_qblocks}, {block_map.n_tiles}]")
+    if block_map.head_map is not None and block_map.head_map.numel() != num_heads:
+        raise GoalForceError(f"flash_attn_sparse.block_map: expected a head_map of [{num_heads}], got [{block_map.head_map.numel()}]")
+    if vt is not None and vt.numel() < num_heads * 128 * kv_pad(skv):
+        raise GoalForceError("flash_attn_sparse.vt: buffer smaller than heads*128*kv_pad")
+    out = _out(out, "flash_attn_sparse.out", sq, hd_all, q.device)
+    if scale is None:
+        scale = 1.0 / math.sqrt(128)
+    lse_t = torch.empty((sq, num_heads), dtype=torch.float32, device=q.device) if lse else None
+    # PROFILE_ATTN's key count is what the launch computes: the selected share of the keys (FLOP figures derived from the list count
+    # 4 Sq Skv d per head; the dense Skv would overstate a sparse launch by 1 / density)
+    with _timed(PROFILE_ATTN, sq, max(1, round(skv * block_map.density)), num_heads):
+        _vt_attn(_lib.load(), q, k, v, vt, out, lse_t, sq, skv, num_heads, 128, scale, True, block_map)
+    return (out, lse_t) if lse else out
 
 
 # ---- SageAttention backend (gf_sage_attention.hip; the recipe is stated in include/goalforce.h)

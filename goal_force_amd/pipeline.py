@@ -58,6 +58,7 @@ class WanVideoPipeline(torch.nn.Module):
         # denoise(): the uncond forward of a CFG step on a second HIP stream, concurrent with the cond forward (same kernels, same
         # bits).  Measured (3 % slower at full size) and left off; a plain attribute, set by whoever wants the A/B.
         self.cfg_streams = False
+        self.sparse_dense_steps = 0           # the first n steps of the schedule run densely under dit.enable_sparse_attention
         self._cfg_side_stream = None
         self.vram_management_enabled = False
         self.elide_zero_controlnet = True
@@ -309,6 +310,8 @@ class WanVideoPipeline(torch.nn.Module):
                 ev0.record()
             shared = dict(latents=latents, timestep=ts, y=y, control_signal_video_latents=control_signal_video_latents,
                           elide_zero_controlnet=self.elide_zero_controlnet)
+            if progress_id < self.sparse_dense_steps:
+                shared["sparse_dense"] = True         # (only passed when set: a caller's own model_fn need not know the keyword)
             if sequence_parallel is not None:
                 shared["sequence_parallel"] = sequence_parallel
             elif getattr(self, "use_unified_sequence_parallel", False):

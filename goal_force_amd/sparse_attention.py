@@ -1,0 +1,83 @@
+"""Block-sparse self-attention patterns for the DiT / ControlNet blocks (dit.enable_sparse_attention).
+
+The mechanism is ops.flash_attn_sparse: kernel 3 over a list of 64-key tiles per 256-row query block (ops.BlockMap).  A pattern
+is any callable `grid -> ops.BlockMap`, grid = the (f, h, w) token grid of the latent video; the blocks ask it for the map of the
+grid they run on.  One family ships, FrameWindow: it needs no token reordering, because the DiT's tokens are already in
+(f, h, w) order and a window of frames is then a band of tiles.
+
+The reference has no counterpart (its flash_attention is dense on every backend), so nothing here is pinned against it, and
+what a sparse pattern does to the videos of a trained checkpoint is NOT measured in this repository: the switch
+is off by default and the tests pin the mechanism — which keys a row sees, and that it sees them with the dense kernel's bits.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import ops
+from ._lib import GoalForceError
+
+__all__ = ["FrameWindow", "frame_window_mask"]
+
+
+def _check_grid(grid):
+    try:
+        f, h, w = (int(x) for x in grid)
+    except (TypeError, ValueError):
+        raise GoalForceError(f"sparse attention: expected a token grid (f, h, w), got {grid!r}") from None
+    if min(f, h, w) < 1:
+        raise GoalForceError(f"sparse attention: expected a token grid (f, h, w) of positive sizes, got {grid!r}")
+    return f, h, w
+
+
+def frame_window_mask(grid, window: int, sink_frames: int = 1) -> torch.Tensor:
+    """The FrameWindow selection as a CPU bool array [n_qblocks, n_tiles] (the definition is FrameWindow's docstring).  Tokens are
+    in frame order, so a block and a tile each cover an INTERVAL of frames and "some frame of the block and some frame of the tile
+    are within `window`" is a test on the intervals' ends."""
+    f, h, w = _check_grid(grid)
+    S, hw = f * h * w, h * w
+    qb, kb = ops.SPARSE_QB, ops.SPARSE_KB
+
+    def frames(step):
+        first = torch.arange(0, S, step)
+        last = torch.clamp(first + step, max=S) - 1
+        return first // hw, last // hw
+
+    q_lo, q_hi = frames(qb)
+    k_lo, k_hi = frames(kb)
+    near = (k_lo[None, :] - q_hi[:, None] <= window) & (q_lo[:, None] - k_hi[None, :] <= window)
+    return near | (k_lo[None, :] < sink_frames)
+
+
+class FrameWindow:
+    """Spatio-temporally local attention as a block-level cover: every query sees the keys of the frames within `window` of its
+    own, plus the first `sink_frames` frames, rounded OUT to whole blocks.  Exactly, for a token grid (f, h, w), S = f h w tokens
+    in (f, h, w) order:
+      * a token's frame is token // (h * w);
+      * query block b covers tokens [256 b, min(256 b + 256, S));
+      * tile t covers tokens [64 t, min(64 t + 64, S));
+      * (b, t) is selected iff some frame fq of the block and some frame fk of the tile satisfy |fq - fk| <= window or
+        fk < sink_frames.
+    So a query also sees the rest of every tile its window touches, and everything its block neighbours see (never less than the
+    token-level window).  One map for all heads.  `pattern(grid)` returns the host-validated ops.BlockMap, `pattern(grid, device)`
+    the copy on that device; both are memoised per (grid, device)."""
+
+    def __init__(self, window: int, sink_frames: int = 1):
+        if int(window) != window or window < 0 or int(sink_frames) != sink_frames or sink_frames < 0:
+            raise GoalForceError(f"FrameWindow: expected non-negative integers, got window={window!r}, sink_frames={sink_frames!r}")
+        self.window, self.sink_frames = int(window), int(sink_frames)
+        self._maps = {}
+
+    def __repr__(self):
+        return f"FrameWindow({self.window}, {self.sink_frames})"
+
+    def mask(self, grid) -> torch.Tensor:
+        return frame_window_mask(grid, self.window, self.sink_frames)
+
+    def __call__(self, grid, device=None) -> ops.BlockMap:
+        grid = _check_grid(grid)
+        key = (grid, None if device is None else str(torch.device(device)))
+        if key not in self._maps:
+            if (grid, None) not in self._maps:
+                self._maps[(grid, None)] = ops.BlockMap(self.mask(grid))
+            self._maps[key] = self._maps[(grid, None)].to(device) if device is not None else self._maps[(grid, None)]
+        return self._maps[key]

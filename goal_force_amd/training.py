@@ -258,6 +258,11 @@ class DiTBlockFn(torch.autograd.Function):
         if getattr(block.self_attn, "_gf_sage", False):
             # no backward exists for the sage backend (nor in the sageattention package): the backward would differentiate another function
             raise GoalForceError("training through a block with enable_sage_attention is refused: call enable_sage_attention(module, False) first")
+        if getattr(block.self_attn, "_gf_sparse", None) is not None:
+            # there is no sparse backward: the backward recomputes and differentiates the DENSE attention, whatever the keep level
+            # (with keep level "none" the forward's own refusal, SelfAttention.attend(keep=...), is never reached)
+            raise GoalForceError("training through a block with enable_sparse_attention is refused (there is no sparse backward): "
+                                 "call enable_sparse_attention(module, None) first")
         ctx.param_needs = [p.requires_grad for p in params]
         ctx.q_prescale = bool(ops._OPT["attn_q_prescale"])       # what the forward's self-attention saw is what the backward rebuilds (dit.SelfAttention.attend)
         keep = ({"wide": True} if _wide_fits(x2) else {}) if KEEP_ATTENTION else None

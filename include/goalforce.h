@@ -172,6 +172,24 @@ GF_API int gf_flash_attn_fwd_vt32(const void* q, const void* k, const void* vt, 
                                   int64_t q_len, int64_t kv_len, int64_t kv_pad, int64_t heads, int64_t head_dim,
                                   int64_t q_stride, int64_t k_stride, int64_t o_stride, float scale, void* stream);
 
+/* gf_flash_attn_fwd_vt32_sparse — gf_flash_attn_fwd_vt32 over a block map: the workgroup of query block b (256 rows) of head h
+ * visits only the 64-key tiles listed for it, softmax and output are taken over those keys alone.  Operands and their checks
+ * are gf_flash_attn_fwd_vt32's (V^T from gf_transpose_v32 / gf_linear_vt32 / gf_linear_vt32_fp8; lse may be NULL).  The map is
+ * CSR in device memory, read-only during the launch:
+ *   row_ptr  int32 [n_maps * n_qblocks + 1], n_qblocks = ceil(q_len / 256);
+ *   tile_idx int32, the tiles of row r at [row_ptr[r], row_ptr[r + 1]);
+ *   head_map int32 [heads] or NULL (every head uses map 0); head h reads row head_map[h] * n_qblocks + b.
+ * Contract: inside a row the indices ascend, there are at least 2 of them (the two-tile pipeline is the validated one: the dense
+ * entry's kv_len >= 128), each is < ceil(kv_len / 64), head_map[h] < n_maps.  The library cannot inspect device memory: it checks
+ * the pointers and n_maps >= 1 only.  The kernel clamps every index it reads to the tiles that exist, so a map that breaks the
+ * contract gives wrong numbers but no read outside k / vt — that clamp is the only protection against a bad map.
+ * A row that lists every tile computes bit for bit what gf_flash_attn_fwd_vt32 does; any row computes bit for bit what
+ * gf_flash_attn_fwd_vt32 does on the listed tiles' keys gathered in order.  Forward only (no backward takes a map). */
+GF_API int gf_flash_attn_fwd_vt32_sparse(const void* q, const void* k, const void* vt, void* o, float* lse,
+                                         const int32_t* row_ptr, const int32_t* tile_idx, const int32_t* head_map, int64_t n_maps,
+                                         int64_t q_len, int64_t kv_len, int64_t kv_pad, int64_t heads, int64_t head_dim,
+                                         int64_t q_stride, int64_t k_stride, int64_t o_stride, float scale, void* stream);
+
 /* gf_linear_vt32 — the V projection of SelfAttention.forward (`v = self.v(x)`, DIT:131-146) written DIRECTLY in the layout
  * gf_flash_attn_fwd_vt32 reads: vt[n * kv_pad + pos(s)] = bf16(sum_k x[s,k] * w[n,k] + bias[n]) for n < N, s < kv_len, positions
  * kv_len .. kv_pad-1 zero, pos() = the key order of gf_transpose_v32.  Bit-identical to gf_gemm_bf16(x, w, bias) followed by
