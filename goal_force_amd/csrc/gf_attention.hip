@@ -19,9 +19,8 @@
 //   * softmax in fp32 in the exp2 domain; lazy rescale (O is only rescaled when the running maximum has moved far enough).
 // The phase-serial first kernel and the measured-and-dropped variants of kernel 3 (ORMAX watch, head-major map, what-if and clock
 // builds) are NOT in this file: tools/patches/attention_experiments.patch re-creates them on top of it (tools/build_variants.sh).
-#include "gf_common.h"
+#include "gf_mfma_frame.h"
 #include <cstdlib>
-#include <type_traits>
 
 namespace {
 
@@ -77,13 +76,6 @@ constexpr int AT2_THREADS = 512;
 constexpr int AT2_V_BASE = 2 * KV_TILE_BYTES;
 constexpr int AT2_LDS = 4 * KV_TILE_BYTES;
 
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
 __device__ __forceinline__ void mfma32(f32x16& acc, const bf16x8& a, const bf16x8& b) {
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
 }
@@ -101,7 +93,7 @@ __global__ __launch_bounds__(AT2_THREADS, 2) void flash_attn_fwd_kernel2(const A
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, h = lane >> 5;
     int head, qb;
-    {
+    {   // gf_xcd_head_block's map, spelled out: the call loads p.n_qblocks ahead of the branch and this kernel's prologue comes out different
         const int pid = blockIdx.x;
         if ((p.heads & 7) == 0) {
             const int xcd = pid & 7, idx = pid >> 3;
@@ -421,7 +413,7 @@ __global__ __launch_bounds__(AT2_THREADS, 2) void flash_attn_fwd_kernel2(const A
         frag_load(std::integral_constant<int, 1>{}, par_c);
         frag_load(std::integral_constant<int, 2>{}, par_c);
         float mx = -INFINITY, mo = 0.f;
-        static_for<0, 4>([&](auto i_c) {
+        gf_static_for<0, 4>([&](auto i_c) {
             constexpr int G = decltype(i_c)::value;
             mfma_op(i_c, par_c);
             frag_load(std::integral_constant<int, G + 3>{}, par_c);
@@ -443,7 +435,7 @@ __global__ __launch_bounds__(AT2_THREADS, 2) void flash_attn_fwd_kernel2(const A
         new_max(mx);
         const float mc = m_run * c;
         float rs = 0.f, pe[2];
-        static_for<4, 32>([&](auto i_c) {
+        gf_static_for<4, 32>([&](auto i_c) {
             constexpr int G = decltype(i_c)::value;
             mfma_op(i_c, par_c);
             frag_load(std::integral_constant<int, G + 3>{}, par_c);
@@ -451,7 +443,7 @@ __global__ __launch_bounds__(AT2_THREADS, 2) void flash_attn_fwd_kernel2(const A
             // scores 0..7 two per slot in slots 4-7, scores 8..31 one per slot in slots 8-31
             constexpr int n_el = (G < 8) ? 2 : 1;
             constexpr int el0 = (G < 8) ? 2 * (G - 4) : G;
-            static_for<0, n_el>([&](auto k_c) {
+            gf_static_for<0, n_el>([&](auto k_c) {
                 constexpr int el = el0 + decltype(k_c)::value, half = el >> 4, e = el & 15;
                 float sv = sc[PAR][half][e];
                 asm volatile("" : "+v"(sv));
@@ -608,19 +600,8 @@ __global__ __launch_bounds__(At3<NQ>::THREADS, (NQ == 2 ? 2 : 1)) void flash_att
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 15, g = lane >> 4;
-    int head, qb0;
-    {
-        const int pid = blockIdx.x;
-        // XCD-aware: the 32 CUs of an XCD walk the query blocks of ONE head together, K / V of that head come from the XCD's L2
-        if ((p.heads & 7) == 0) {
-            const int xcd = pid & 7, idx = pid >> 3;
-            head = xcd + 8 * (idx / p.n_qblocks);
-            qb0 = idx % p.n_qblocks;
-        } else {
-            head = pid / p.n_qblocks;
-            qb0 = pid % p.n_qblocks;
-        }
-    }
+    int head, qb0;   // XCD-aware: the 32 CUs of an XCD walk the query blocks of ONE head together, K / V of that head come from the XCD's L2
+    gf_xcd_head_block(blockIdx.x, p.heads, p.n_qblocks, head, qb0);
     const int q0 = qb0 * QB + wave * RW;
 
     int vt_last = 0;     // sparse: the last V^T tile that exists (set with the list below)
@@ -938,11 +919,11 @@ __global__ __launch_bounds__(At3<NQ>::THREADS, (NQ == 2 ? 2 : 1)) void flash_att
     auto phase = [&](auto par_c, int pidx) __attribute__((always_inline)) {
         constexpr int PAR = decltype(par_c)::value;
         apply_pending();
-        static_for<0, RING - 1>([&](auto f_c) { frag_load(f_c, par_c); });
+        gf_static_for<0, RING - 1>([&](auto f_c) { frag_load(f_c, par_c); });
         float mx[NQ];
 #pragma unroll
         for (int qb = 0; qb < NQ; ++qb) mx[qb] = -INFINITY;
-        static_for<0, 4 * NQ>([&](auto s_c) {
+        gf_static_for<0, 4 * NQ>([&](auto s_c) {
             constexpr int S = decltype(s_c)::value;
             mfma_op(s_c, par_c);
             if constexpr (S % NQ == 0) frag_load(std::integral_constant<int, S / NQ + RING - 1>{}, par_c);
@@ -957,7 +938,7 @@ __global__ __launch_bounds__(At3<NQ>::THREADS, (NQ == 2 ? 2 : 1)) void flash_att
         });
         new_max(par_c, mx, false);
         float pe[2];
-        static_for<4 * NQ, NS>([&](auto s_c) {
+        gf_static_for<4 * NQ, NS>([&](auto s_c) {
             constexpr int S = decltype(s_c)::value;
             mfma_op(s_c, par_c);
             // the row-sum MFMAs of PV(p-1) ride in the PV half: after the last slot that reads pf[kk]
@@ -1172,19 +1153,6 @@ static int flash_attn_fwd_impl(const void* q, const void* k, const void* v, void
     GF_CHECK_ARG((kv_len + 64) * k_stride < (1LL << 31) && (kv_len + 64) * v_stride < (1LL << 31),
                  "gf_flash_attn_fwd: kv_len*stride must stay below 2^31 elements");
     if (q_len == 0) return GF_OK;
-    static GfDeviceOnce once;
-    hipError_t e = gf_once_per_device(once, [] {
-        hipError_t r = hipFuncSetAttribute(reinterpret_cast<const void*>(flash_attn_fwd_kernel2<false>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, AT2_LDS);
-        if (r == hipSuccess)
-            r = hipFuncSetAttribute(reinterpret_cast<const void*>(flash_attn_fwd_kernel2<true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, AT2_LDS);
-        return r;
-    });
-    if (e != hipSuccess) {
-        gf_set_error("gf_flash_attn_fwd: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-        return GF_ERR_LAUNCH;
-    }
     AttnArgs a;
     a.q = (const u16*)q;
     a.k = (const u16*)k;
@@ -1209,14 +1177,10 @@ static int flash_attn_fwd_impl(const void* q, const void* k, const void* v, void
         a.last_key_bias = log2f(last_key_multiplicity) / a.scale_log2e;
     }
     a.dbg = nullptr;
-    if (vt)
-        hipLaunchKernelGGL(flash_attn_fwd_kernel2<true>, dim3((unsigned)(a.n_qblocks * a.heads)), dim3(AT2_THREADS), AT2_LDS,
-                           (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL(flash_attn_fwd_kernel2<false>, dim3((unsigned)(a.n_qblocks * a.heads)), dim3(AT2_THREADS), AT2_LDS,
-                           (hipStream_t)stream, a);
-    GF_CHECK_LAUNCH("gf_flash_attn_fwd");
-    return GF_OK;
+    const dim3 grid((unsigned)(a.n_qblocks * a.heads)), block(AT2_THREADS);
+    const char* fn = "gf_flash_attn_fwd";
+    return vt ? gf_launch_lds<flash_attn_fwd_kernel2<true>>(fn, GF_ATTR_MSG_PLAIN, fn, grid, block, AT2_LDS, (hipStream_t)stream, a)
+              : gf_launch_lds<flash_attn_fwd_kernel2<false>>(fn, GF_ATTR_MSG_PLAIN, fn, grid, block, AT2_LDS, (hipStream_t)stream, a);
 }
 
 extern "C" GF_API int gf_flash_attn_fwd(const void* q, const void* k, const void* v, void* o, int64_t q_len, int64_t kv_len,
@@ -1300,19 +1264,6 @@ static int flash_attn_vt32_impl(const char* fn, const void* q, const void* k, co
         GF_CHECK_ARG(n_maps >= 1 && n_maps * n_qblocks < (1LL << 31) - 1, "%s: n_maps=%ld (at least 1; n_maps * query blocks below 2^31)", fn,
                      (long)n_maps);
     if (q_len == 0) return GF_OK;
-    static GfDeviceOnce once;
-    hipError_t e = gf_once_per_device(once, [] {
-        hipError_t r = hipFuncSetAttribute(reinterpret_cast<const void*>(flash_attn_fwd_kernel3<K3_NQ, false>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, AT3_LDS);
-        if (r == hipSuccess)
-            r = hipFuncSetAttribute(reinterpret_cast<const void*>(flash_attn_fwd_kernel3<K3_NQ, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, AT3_LDS);
-        return r;
-    });
-    if (e != hipSuccess) {
-        gf_set_error("%s: hipFuncSetAttribute failed: %s", fn, hipGetErrorString(e));
-        return GF_ERR_LAUNCH;
-    }
     AttnArgs a;
     a.q = (const u16*)q;
     a.k = (const u16*)k;
@@ -1337,12 +1288,8 @@ static int flash_attn_vt32_impl(const char* fn, const void* q, const void* k, co
     a.head_map = head_map;
     a.n_maps = (int)n_maps;
     const dim3 grid((unsigned)(a.n_qblocks * a.heads)), block(At3<K3_NQ>::THREADS);
-    if (sparse)
-        hipLaunchKernelGGL((flash_attn_fwd_kernel3<K3_NQ, true>), grid, block, AT3_LDS, (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL((flash_attn_fwd_kernel3<K3_NQ, false>), grid, block, AT3_LDS, (hipStream_t)stream, a);
-    GF_CHECK_LAUNCH(fn);
-    return GF_OK;
+    return sparse ? gf_launch_lds<flash_attn_fwd_kernel3<K3_NQ, true>>(fn, GF_ATTR_MSG_PLAIN, fn, grid, block, AT3_LDS, (hipStream_t)stream, a)
+                  : gf_launch_lds<flash_attn_fwd_kernel3<K3_NQ, false>>(fn, GF_ATTR_MSG_PLAIN, fn, grid, block, AT3_LDS, (hipStream_t)stream, a);
 }
 
 extern "C" GF_API int gf_flash_attn_fwd_vt32(const void* q, const void* k, const void* vt, void* o, float* lse, int64_t q_len,

@@ -9,8 +9,7 @@
 // v_mfma_f32_16x16x32_bf16; the design notes stand in front of them below.  The first kernels (32x32x16 MFMAs, separate dQ / dV / dK
 // passes, 8 products), the 32-key dK/dV kernel and the pre-scaled-Q variant are NOT in this file:
 // tools/patches/attention_bwd_experiments.patch re-creates them.
-#include "gf_common.h"
-#include <type_traits>
+#include "gf_mfma_frame.h"
 
 namespace {
 
@@ -119,17 +118,6 @@ __device__ __forceinline__ bf16x8 pack44(const f32x4& a, const f32x4& b) {
     const u32x4 w = {pack2bf(a[0], a[1]), pack2bf(a[2], a[3]), pack2bf(b[0], b[1]), pack2bf(b[2], b[3])};
     return __builtin_bit_cast(bf16x8, w);
 }
-// XCD-aware block order (as the forward): the blocks of one head run on one XCD, whose L2 then holds that head's streamed operands
-__device__ __forceinline__ void head_block(int pid, int heads, int nblk, int& head, int& blk) {
-    if ((heads & 7) == 0) {
-        const int xcd = pid & 7, idx = pid >> 3;
-        head = xcd + 8 * (idx / nblk);
-        blk = idx % nblk;
-    } else {
-        head = pid / nblk;
-        blk = pid % nblk;
-    }
-}
 // descriptor over rows row0 .. len - 1 of a [len, stride] bf16 tensor, head column offset included: rows >= len read as zeros
 __device__ __forceinline__ u32x4s rows_srd(const u16* base, long stride, int head, int row0, int len) {
     const int rem = len - row0;
@@ -179,7 +167,7 @@ __global__ __launch_bounds__(DQ_THREADS, 2) void attn_bwd_dq16_kernel(const Bwd1
     const int r = lane & 15, g = lane >> 4;
     const int nqb = (p.q_len + DQ_ROWS - 1) / DQ_ROWS;
     int head, qblk;
-    head_block(blockIdx.x, p.heads, nqb, head, qblk);
+    gf_xcd_head_block(blockIdx.x, p.heads, nqb, head, qblk);
     const int q0 = qblk * DQ_ROWS + wave * 32;
 
     bf16x8 qf[2][4], dof[2][4];      // B operands: Q^T / dO^T [32 d x 16 queries]: lane = query column, 8 d at 32 ks + 8 g
@@ -401,7 +389,7 @@ __global__ __launch_bounds__(Kv48::THREADS) void attn_bwd_dkv48_kernel(const Bwd
     const int pair = roleB ? wave - L::NP : wave;
     const int nkb = (p.kv_len + L::ROWS - 1) / L::ROWS;
     int head, kblk;
-    head_block(blockIdx.x, p.heads, nkb, head, kblk);
+    gf_xcd_head_block(blockIdx.x, p.heads, nkb, head, kblk);
     const int k0 = kblk * L::ROWS + pair * (16 * KB);
 
     bf16x8 own[KB][4];               // wave A: K^T, wave B: V^T [32 d x 16 keys] per key block
@@ -634,16 +622,9 @@ extern "C" GF_API int gf_flash_attn_bwd(const void* q, const void* k, const void
     GF_CHECK_ARG((q_len + 64) * q_stride * 2 < (1LL << 32) &&
                      (q_len + 64) * do_stride * 2 < (1LL << 32) && (kv_len + 64) * k_stride * 2 < (1LL << 32) && (kv_len + 64) * v_stride * 2 < (1LL << 32),
                  "gf_flash_attn_bwd: a sequence (len x stride) must stay below 4 GiB");
-    static GfDeviceOnce once;
-    hipError_t e = gf_once_per_device(once, [] {
-        hipError_t r = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dq16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, DQ16_LDS);
-        if (r != hipSuccess) return r;
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dkv48_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, Kv48::LDS);
-    });
-    if (e != hipSuccess) {
-        gf_set_error("gf_flash_attn_bwd: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-        return GF_ERR_LAUNCH;
-    }
+    // both kernels are armed before the first launch: a failure here leaves the workspace untouched
+    if (const int rc = gf_arm_lds<attn_bwd_dq16_kernel>("gf_flash_attn_bwd", GF_ATTR_MSG_PLAIN, DQ16_LDS)) return rc;
+    if (const int rc = gf_arm_lds<attn_bwd_dkv48_kernel>("gf_flash_attn_bwd", GF_ATTR_MSG_PLAIN, Kv48::LDS)) return rc;
     Bwd16Args b;
     BwdArgs& a = b.b;
     a.q = (const u16*)q; a.k = (const u16*)k; a.v = (const u16*)v; a.o = (const u16*)o; a.dout = (const u16*)dout;

@@ -14,9 +14,8 @@
 // Arithmetic: every output element sums its products in the order of the implicit GEMM (K = (dt, dy, dx, cin), 32 channels per
 // v_mfma_f32_16x16x32_bf16, one accumulation chain from tile 0), bias added in fp32, ONE rounding to bf16, the residual added to the
 // rounded value and rounded again — bit-identical to gf_conv3d_bf16 (tests/test_vae.py).
-#include "gf_common.h"
+#include "gf_mfma_frame.h"
 #include "gf_conv_a4_loop.inc"
-#include <type_traits>
 
 namespace {
 
@@ -37,20 +36,6 @@ struct ConvA4Args {
     int tiles_m, tiles_n;
 };
 
-template <int I>
-__device__ __forceinline__ float ca_acc() {
-    float x;
-    asm volatile("v_accvgpr_read_b32 %0, a[%1]" : "=v"(x) : "n"(I));
-    return x;
-}
-template <int I, int N, class F>
-__device__ __forceinline__ void ca_static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        ca_static_for<I + 1, N>(f);
-    }
-}
-
 template <int EPI>
 __global__ __launch_bounds__(CA_THREADS, 1) void conv_a4_kernel(const ConvA4Args p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -64,22 +49,13 @@ __global__ __launch_bounds__(CA_THREADS, 1) void conv_a4_kernel(const ConvA4Args
     // workgroup -> tile: an XCD (blockIdx % 8) walks a CONTIGUOUS range of row tiles (neighbouring row tiles read overlapping buffer
     // rows — a tap shifts the window by at most two pixel rows — so an XCD's L2 serves most of the nine spatial taps' re-reads), the
     // column tiles of a row tile back to back
-    const int nwg = p.tiles_m * p.tiles_n;
-    int v;
-    {
-        const int pid = blockIdx.x;
-        const int xcd = pid & 7, local = pid >> 3;
-        const int q = nwg >> 3, r = nwg & 7;
-        v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
-    }
+    const int v = gf_xcd_tile_order(p.tiles_m * p.tiles_n);
     const int m0 = (v / p.tiles_n) * CA_BM, n0 = (v % p.tiles_n) * CA_BN;
 
     // ---- staging: piece q of wave w = rows 32 q + 8 w .. + 7 of the tile; lane l fills LDS chunk (l & 7) of row (l >> 3) and
     // fetches logical chunk (l & 7) ^ (row & 7) of that row (the GEMM's XOR-swizzled 128-byte-row image)
-    const int srow = lane >> 3;
     const unsigned rowA = (unsigned)p.C * 2u, rowB = (unsigned)p.ldw * 2u;        // bytes per buffer row / weight row
-    unsigned voffA = (unsigned)srow * rowA + (unsigned)(((lane & 7) ^ srow) << 4);
-    unsigned voffB = (unsigned)srow * rowB + (unsigned)(((lane & 7) ^ srow) << 4);
+    unsigned voffA = gf_a4_voff<2>(lane, (unsigned)p.C), voffB = gf_a4_voff<2>(lane, (unsigned)p.ldw);
     const unsigned long baseA = (unsigned long)((const char*)p.xp + (long)m0 * rowA);
     const unsigned long baseB = (unsigned long)((const char*)p.w + (long)n0 * rowB);
     const unsigned aLo = (unsigned)baseA, aHi = (unsigned)(baseA >> 32) & 0xffffu;
@@ -146,15 +122,15 @@ __global__ __launch_bounds__(CA_THREADS, 1) void conv_a4_kernel(const ConvA4Args
                                        : u16x8{0, 0, 0, 0, 0, 0, 0, 0};
             }
     }
-    ca_static_for<0, 6>([&](auto j_c) {
+    gf_static_for<0, 6>([&](auto j_c) {
         constexpr int j = decltype(j_c)::value;
         const float bv[4] = {bf2f(bpre[j][0]), bf2f(bpre[j][1]), bf2f(bpre[j][2]), bf2f(bpre[j][3])};
-        ca_static_for<0, 8>([&](auto i_c) {
+        gf_static_for<0, 8>([&](auto i_c) {
             constexpr int i = decltype(i_c)::value;
             constexpr int A0 = (i * 8 + j) * 4;
             u32x2 pk;
-            pk[0] = pack2bf(ca_acc<A0>() + bv[0], ca_acc<A0 + 1>() + bv[1]);
-            pk[1] = pack2bf(ca_acc<A0 + 2>() + bv[2], ca_acc<A0 + 3>() + bv[3]);
+            pk[0] = pack2bf(gf_agpr_read<A0>() + bv[0], gf_agpr_read<A0 + 1>() + bv[1]);
+            pk[1] = pack2bf(gf_agpr_read<A0 + 2>() + bv[2], gf_agpr_read<A0 + 3>() + bv[3]);
             const int row = i * 16 + frow;
             const int slot = (j * 4 + fq) ^ ((row & 15) << 1);
             *(GF_LDS u32x2*)(ep + row * 256 + slot * 8) = pk;
@@ -188,17 +164,8 @@ __global__ __launch_bounds__(CA_THREADS, 1) void conv_a4_kernel(const ConvA4Args
 
 template <int EPI>
 int launch_conv_a4(const ConvA4Args& a, hipStream_t stream) {
-    static GfDeviceOnce once;
-    hipError_t e = gf_once_per_device(once, [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(conv_a4_kernel<EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, CA_LDS);
-    });
-    if (e != hipSuccess) {
-        gf_set_error("gf_conv3d_padded_bf16: hipFuncSetAttribute(%d B LDS) failed: %s", CA_LDS, hipGetErrorString(e));
-        return GF_ERR_LAUNCH;
-    }
-    hipLaunchKernelGGL((conv_a4_kernel<EPI>), dim3((unsigned)(a.tiles_m * a.tiles_n)), dim3(CA_THREADS), CA_LDS, stream, a);
-    GF_CHECK_LAUNCH("gf_conv3d_padded_bf16");
-    return GF_OK;
+    return gf_launch_lds<conv_a4_kernel<EPI>>("gf_conv3d_padded_bf16", GF_ATTR_MSG_BYTES, "gf_conv3d_padded_bf16", dim3((unsigned)(a.tiles_m * a.tiles_n)),
+                                              dim3(CA_THREADS), CA_LDS, stream, a);
 }
 
 }  // namespace

@@ -24,8 +24,7 @@
 // Every output element sums its products in the order of the implicit GEMM (taps (dt, dy, dx) in sequence, 32 channels per MFMA):
 // the results are BIT-IDENTICAL to gemm_ph_kernel<CONV> (tests/test_vae.py).  Frames are cut into segments so that a launch has a
 // few workgroups per CU; a segment's first two input frames only feed the later temporal taps.
-#include "gf_common.h"
-#include <type_traits>
+#include "gf_mfma_frame.h"
 
 namespace {
 
@@ -67,10 +66,6 @@ struct CdArgs {
 // which turns a ring that is two taps deep into one that is one tap deep.
 #define CD_WAIT_BARRIER(N) asm volatile("s_waitcnt vmcnt(" #N ")\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
-__device__ __forceinline__ void cd_glds16(const void* g, GF_LDS char* l) {
-    __builtin_amdgcn_global_load_lds((const GF_GLOBAL void*)g, (GF_LDS void*)l, 16, 0, 0);
-}
-
 template <int EPI, int NCB>
 __global__ __launch_bounds__(CD_THREADS, 2) void conv3d_c96_kernel(const CdArgs p) {
     using SH = CdShape<NCB>;
@@ -109,7 +104,7 @@ __global__ __launch_bounds__(CD_THREADS, 2) void conv3d_c96_kernel(const CdArgs 
             if (i < CD_W_INSTR) {
                 int o = woff[k];
                 asm volatile("" : "+v"(o));                // opaque: nine hoisted 64-bit row addresses (one per slot and piece) cost more registers than three adds per piece
-                cd_glds16(o < 0 ? (const char*)p.zero : (const char*)p.w + o + tap * (CD_C * 2), wbuf + stage_off + i * 1024);
+                glds16(o < 0 ? (const char*)p.zero : (const char*)p.w + o + tap * (CD_C * 2), wbuf + stage_off + i * 1024);
             }
         }
     };
@@ -126,7 +121,7 @@ __global__ __launch_bounds__(CD_THREADS, 2) void conv3d_c96_kernel(const CdArgs 
                 const int hy = px / CD_HW, hx = px - hy * CD_HW;
                 const int y = y0 - 1 + hy, x = x0 - 1 + hx;
                 const bool ok = px < CD_HH * CD_HW && sl < 12 && y >= 0 && y < p.H && x >= 0 && x < p.W;
-                cd_glds16(ok ? base + (long)((y * p.W + x) * (CD_C * 2) + sl * 16) : (const char*)p.zero, halo + i * 1024);
+                glds16(ok ? base + (long)((y * p.W + x) * (CD_C * 2) + sl * 16) : (const char*)p.zero, halo + i * 1024);
             }
         }
     };
@@ -392,7 +387,7 @@ __global__ __launch_bounds__(CD_THREADS, 1) void conv2d_up_c192_kernel(const UpA
 #pragma unroll
         for (int k = 0; k < WK; ++k) {
             const int i = wave + CD_WAVES * k;
-            if (i < W_INSTR) cd_glds16((const char*)p.w + woff[k] + stage * (CD_C * 2), wbuf + stage_off + i * 1024);
+            if (i < W_INSTR) glds16((const char*)p.w + woff[k] + stage * (CD_C * 2), wbuf + stage_off + i * 1024);
         }
     };
     const bool more = wave + CD_WAVES * (WK - 1) < W_INSTR;          // 3 weight requests per stage (else 2)
@@ -408,7 +403,7 @@ __global__ __launch_bounds__(CD_THREADS, 1) void conv2d_up_c192_kernel(const UpA
                 const int hy = px / UP_HW, hx = px - hy * UP_HW;
                 const int y = sy0 + hy, x = sx0 + hx;
                 const bool ok = px < UP_HH * UP_HW && sl < 24 && y >= 0 && y < Hs && x >= 0 && x < Ws;
-                cd_glds16(ok ? base + (long)((y * Ws + x) * (UP_C * 2) + sl * 16) : (const char*)p.zero, hbuf + i * 1024);
+                glds16(ok ? base + (long)((y * Ws + x) * (UP_C * 2) + sl * 16) : (const char*)p.zero, hbuf + i * 1024);
             }
         }
     };
@@ -535,18 +530,8 @@ __global__ __launch_bounds__(CD_THREADS, 1) void conv2d_up_c192_kernel(const UpA
 
 template <int EPI, int NCB>
 int launch_cd(const CdArgs& a, unsigned grid, hipStream_t stream) {
-    static GfDeviceOnce once;
-    hipError_t e = gf_once_per_device(once, [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(conv3d_c96_kernel<EPI, NCB>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   CdShape<NCB>::LDS);
-    });
-    if (e != hipSuccess) {
-        gf_set_error("gf_conv3d_bf16 (direct): hipFuncSetAttribute(%d B LDS) failed: %s", CdShape<NCB>::LDS, hipGetErrorString(e));
-        return GF_ERR_LAUNCH;
-    }
-    hipLaunchKernelGGL((conv3d_c96_kernel<EPI, NCB>), dim3(grid), dim3(CD_THREADS), CdShape<NCB>::LDS, stream, a);
-    GF_CHECK_LAUNCH("gf_conv3d_bf16 (direct)");
-    return GF_OK;
+    return gf_launch_lds<conv3d_c96_kernel<EPI, NCB>>("gf_conv3d_bf16 (direct)", GF_ATTR_MSG_BYTES, "gf_conv3d_bf16 (direct)", dim3(grid), dim3(CD_THREADS),
+                                                      CdShape<NCB>::LDS, stream, a);
 }
 
 }  // namespace
@@ -613,15 +598,6 @@ int gf_conv2d_up_direct_c192(const void* src0, const void* Wm, int64_t ldw, cons
     if (nseg < 1) nseg = 1;
     a.tseg = (int)((T_out + nseg - 1) / nseg);
     nseg = (T_out + a.tseg - 1) / a.tseg;
-    static GfDeviceOnce once;
-    hipError_t e = gf_once_per_device(once, [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(conv2d_up_c192_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, UP_LDS);
-    });
-    if (e != hipSuccess) {
-        gf_set_error("gf_conv3d_bf16 (direct upsample): hipFuncSetAttribute(%d B LDS) failed: %s", UP_LDS, hipGetErrorString(e));
-        return GF_ERR_LAUNCH;
-    }
-    hipLaunchKernelGGL(conv2d_up_c192_kernel, dim3((unsigned)(spatial * nseg)), dim3(CD_THREADS), UP_LDS, (hipStream_t)stream, a);
-    GF_CHECK_LAUNCH("gf_conv3d_bf16 (direct upsample)");
-    return GF_OK;
+    return gf_launch_lds<conv2d_up_c192_kernel>("gf_conv3d_bf16 (direct upsample)", GF_ATTR_MSG_BYTES, "gf_conv3d_bf16 (direct upsample)",
+                                                dim3((unsigned)(spatial * nseg)), dim3(CD_THREADS), UP_LDS, (hipStream_t)stream, a);
 }

@@ -20,9 +20,8 @@
 //     walked in groups of 8 M-tiles x all N-tiles so the 32 co-resident blocks of an XCD share
 //     A/W panels through that XCD's L2.
 //   * M and N tails: loads clamp the row index, stores are masked.
-#include "gf_common.h"
+#include "gf_mfma_frame.h"
 #include <cstdlib>
-#include <type_traits>
 
 // The first bf16 kernels that no longer ship (the one-barrier 8-wave kernel in bf16, the slot-scheduled `sl` / `sl8` kernels) and the
 // stamp / what-if / alternative-loop diagnostic builds are NOT in this file: tools/patches/gemm_experiments.patch re-creates them.
@@ -77,10 +76,6 @@ struct GemmArgs {
 // order, bias per ROW, columns >= wrows zero
 constexpr int GF_EPI_VT32 = 6;
 
-__device__ __forceinline__ void glds16(const void* g, GF_LDS char* l) {
-    __builtin_amdgcn_global_load_lds((const GF_GLOBAL void*)g, (GF_LDS void*)l, 16, 0, 0);
-}
-
 typedef __attribute__((ext_vector_type(8))) int i32x8;
 
 // The Linear's own output is rounded to bf16 before anything else happens to it.  Where the epilogue applies a function to it
@@ -95,15 +90,12 @@ __device__ __forceinline__ float gf_epi_act(float lin) {
     } else return lin;
 }
 
-// FP8 = false: A/W are bf16, K-step 64 elements.  FP8 = true: A/W are OCP e4m3 bytes, K-step 128 elements — the
-// LDS image is the same 128-byte rows, each lane's fragment is 32 consecutive k (two 16-byte chunks) and the
-// product runs on v_mfma_scale_f32_16x16x128_f8f6f4 with unit (E8M0 = 127) block scales: 2x the bf16 MFMA rate.
-// p.lda / p.ldw / p.K are in ELEMENTS of the operand type; the staging code works in 16-byte chunks.
+// The fp8 GEMM of the small shapes (M < 512): A/W are OCP e4m3 bytes, K-step 128 elements = one 128-byte LDS row, each lane's
+// fragment is 32 consecutive k (two 16-byte chunks) and the product runs on v_mfma_scale_f32_16x16x128_f8f6f4 with unit
+// (E8M0 = 127) block scales: 2x the bf16 MFMA rate.  p.lda / p.ldw / p.K are in elements = bytes.
 template <int EPI, bool FP8>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_kernel(const GemmArgs p) {
     static_assert(FP8, "only the fp8 form of this kernel ships (launch_gemm); bf16 with M < 512 runs gemm_ph_kernel");
-    constexpr int ESZ = FP8 ? 1 : 2;          // bytes per operand element
-    constexpr int BKE = 128 / ESZ;            // K elements per 128-byte tile row
     extern __shared__ __attribute__((aligned(16))) char smem[];
     GF_LDS char* lds = (GF_LDS char*)smem;
 
@@ -112,14 +104,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_kernel(const GemmArgs p)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
     // ---- XCD-aware tile mapping (bijective for any grid size) ------------------------------
-    const int nwg = p.tiles_m * p.tiles_n;
-    int v;
-    {
-        const int pid = blockIdx.x;
-        const int xcd = pid & 7, local = pid >> 3;
-        const int q = nwg >> 3, r = nwg & 7;
-        v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
-    }
+    const int v = gf_xcd_tile_order(p.tiles_m * p.tiles_n);
     const int per_group = GROUP_M * p.tiles_n;
     const int group = v / per_group;
     const int first_m = group * GROUP_M;
@@ -141,8 +126,8 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_kernel(const GemmArgs p)
         const int row = (wave * 4 + i) * 8 + srow;
         const int am = min(m0 + row, p.M - 1);
         const int bn = min(n0 + row, p.N - 1);
-        a_src[i] = (const char*)p.A + ((long)am * p.lda) * ESZ + schunk * 16;
-        b_src[i] = (const char*)p.W + ((long)bn * p.ldw) * ESZ + schunk * 16;
+        a_src[i] = (const char*)p.A + (long)am * p.lda + schunk * 16;
+        b_src[i] = (const char*)p.W + (long)bn * p.ldw + schunk * 16;
     }
     auto stage = [&](int buf, int kt) {
         GF_LDS char* sa = lds + buf * STAGE_BYTES + wave * 4096;
@@ -158,14 +143,12 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_kernel(const GemmArgs p)
     // ---- fragment read addresses ---------------------------------------------------------------
     const int wm = wave >> 2, wn = wave & 3;
     const int frow = lane & 15;   // row inside a 16-row fragment
-    const int fq = lane >> 4;     // k-chunk (8 elements) inside a 32-deep MFMA step
+    const int fq = lane >> 4;     // 32-byte k group of the row
     // byte offset of (row, chunk) in a tile: row*128 + ((chunk ^ (row&7)) << 4); row&7 == frow&7
     // because all fragment bases are multiples of 16.
     const int sw = frow & 7;
     const int a_base = (wm * 128 + frow) * 128;
     const int b_base = TILE_BYTES + (wn * 64 + frow) * 128;
-    const int ch0 = ((0 * 4 + fq) ^ sw) << 4;   // k-substep 0
-    const int ch1 = ((1 * 4 + fq) ^ sw) << 4;   // k-substep 1
 
     f32x4 acc[8][4];
 #pragma unroll
@@ -173,50 +156,31 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_kernel(const GemmArgs p)
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    const int nk = p.K / BKE;
+    const int nk = p.K / 128;
     stage(0, 0);
     for (int kt = 0; kt < nk; ++kt) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();  // tile kt landed for every wave; everyone is done reading the other buffer
         if (kt + 1 < nk) stage((kt + 1) & 1, kt + 1);
         GF_LDS char* sbuf = lds + (kt & 1) * STAGE_BYTES;
-        if constexpr (!FP8) {
+        // lane (row = lane&15, kb = lane>>4) holds bytes [32kb, 32kb+32) of its row = chunks 2kb, 2kb+1.
+        // A and W fragments are loaded by the same rule, so slot e of lane-group kb pairs the same k on both.
+        const int c0 = ((2 * fq) ^ sw) << 4, c1 = ((2 * fq + 1) ^ sw) << 4;
+        i32x8 bfr[4];
 #pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                const int ch = ks ? ch1 : ch0;
-                bf16x8 af[8], bfr[4];
+        for (int j = 0; j < 4; ++j) {
+            const u32x4 lo = *(GF_LDS u32x4*)(sbuf + b_base + j * 2048 + c0);
+            const u32x4 hi = *(GF_LDS u32x4*)(sbuf + b_base + j * 2048 + c1);
+            bfr[j] = i32x8{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
+        }
 #pragma unroll
-                for (int i = 0; i < 8; ++i) af[i] = *(GF_LDS bf16x8*)(sbuf + a_base + i * 2048 + ch);
+        for (int i = 0; i < 8; ++i) {
+            const u32x4 lo = *(GF_LDS u32x4*)(sbuf + a_base + i * 2048 + c0);
+            const u32x4 hi = *(GF_LDS u32x4*)(sbuf + a_base + i * 2048 + c1);
+            const i32x8 af = i32x8{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
 #pragma unroll
-                for (int j = 0; j < 4; ++j) bfr[j] = *(GF_LDS bf16x8*)(sbuf + b_base + j * 2048 + ch);
-#pragma unroll
-                for (int i = 0; i < 8; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        // swapped operands: D[n-local][m-local]; lane holds 4 consecutive n of one m
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);
-            }
-        } else {
-            // lane (row = lane&15, kb = lane>>4) holds bytes [32kb, 32kb+32) of its row = chunks 2kb, 2kb+1.
-            // A and W fragments are loaded by the same rule, so slot e of lane-group kb pairs the same k on both.
-            const int c0 = ((2 * fq) ^ sw) << 4, c1 = ((2 * fq + 1) ^ sw) << 4;
-            i32x8 bfr[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const u32x4 lo = *(GF_LDS u32x4*)(sbuf + b_base + j * 2048 + c0);
-                const u32x4 hi = *(GF_LDS u32x4*)(sbuf + b_base + j * 2048 + c1);
-                bfr[j] = i32x8{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
-            }
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const u32x4 lo = *(GF_LDS u32x4*)(sbuf + a_base + i * 2048 + c0);
-                const u32x4 hi = *(GF_LDS u32x4*)(sbuf + a_base + i * 2048 + c1);
-                const i32x8 af = i32x8{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(bfr[j], af, acc[i][j], 0, 0, 0,
-                                                                                  0x7F7F7F7F, 0, 0x7F7F7F7F);
-            }
+            for (int j = 0; j < 4; ++j)   // swapped operands: D[n-local][m-local]; lane holds 4 consecutive n of one m
+                acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(bfr[j], af, acc[i][j], 0, 0, 0, 0x7F7F7F7F, 0, 0x7F7F7F7F);
         }
     }
 
@@ -238,12 +202,9 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_kernel(const GemmArgs p)
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 float y[4];
-                float rs = 1.0f;
-                if constexpr (FP8) rs = p.row_scale[min(m0 + wm * 128 + i * 16 + frow, p.M - 1)];
+                const float rs = p.row_scale[min(m0 + wm * 128 + i * 16 + frow, p.M - 1)];   // scale_a of the row
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    y[r] = gf_epi_act<EPI>(acc[i][j][r] * rs + bv[r]);  // (x scale_a for fp8)
-                }
+                for (int r = 0; r < 4; ++r) y[r] = gf_epi_act<EPI>(acc[i][j][r] * rs + bv[r]);
                 u32x2 pk;
                 pk[0] = pack2bf(y[0], y[1]);
                 pk[1] = pack2bf(y[2], y[3]);
@@ -336,14 +297,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_ph_kernel(const GemmArgs
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 2, wc = wave & 3;
 
-    const int nwg = p.tiles_m * p.tiles_n;
-    int v;
-    {
-        const int pid = blockIdx.x;
-        const int xcd = pid & 7, local = pid >> 3;
-        const int q = nwg >> 3, r = nwg & 7;
-        v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
-    }
+    const int v = gf_xcd_tile_order(p.tiles_m * p.tiles_n);
     const int per_group = GROUP_M * p.tiles_n;
     const int group = v / per_group;
     const int first_m = group * GROUP_M;
@@ -757,20 +711,6 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_ph_kernel(const GemmArgs
 #include "gf_gemm_a4f8_loop.inc"   // the fp8 K loop (tools/gen_gemm_a4f8.py)
 constexpr int A4_THREADS = 256;
 
-template <int I>
-__device__ __forceinline__ float a4_acc() {
-    float x;
-    asm volatile("v_accvgpr_read_b32 %0, a[%1]" : "=v"(x) : "n"(I));
-    return x;
-}
-template <int I, int N, class F>
-__device__ __forceinline__ void a4_static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        a4_static_for<I + 1, N>(f);
-    }
-}
-
 // FP8 = true (gf_gemm_fp8, the reference's fp8_linear contract VRAM:115-151): the operands are OCP e4m3 bytes, a K tile is still
 // 128 bytes per row (= 128 elements, one k step of v_mfma_f32_16x16x128_f8f6f4), the loop is gf_gemm_a4f8_loop.inc (two barriers
 // per tile, staging by half tiles: tools/gen_gemm_a4f8.py) and the epilogue multiplies each row by its activation scale first.
@@ -785,14 +725,7 @@ __global__ __launch_bounds__(A4_THREADS, 1) void gemm_a4_kernel(const GemmArgs p
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
 
-    const int nwg = p.tiles_m * p.tiles_n;
-    int v;
-    {
-        const int pid = blockIdx.x;
-        const int xcd = pid & 7, local = pid >> 3;
-        const int q = nwg >> 3, r = nwg & 7;
-        v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
-    }
+    const int v = gf_xcd_tile_order(p.tiles_m * p.tiles_n);
     const int gm = p.group_m;                        // row tiles per group (launch_gemm_a4: 8, or 4 for long K loops)
     const int per_group = gm * p.tiles_n;
     const int group = v / per_group;
@@ -804,9 +737,7 @@ __global__ __launch_bounds__(A4_THREADS, 1) void gemm_a4_kernel(const GemmArgs p
     // ---- staging: wave w fills 64 rows of both operand tiles as 8 pieces of 8 rows x 128 B (GF_A4_ROWMAP: piece p = rows
     // 32 p + 8 w .., the four waves interleaved; else rows 64 w + 8 p ..); lane l of a piece
     // fills LDS chunk (l & 7) of row (l >> 3) and must fetch logical chunk (l & 7) ^ (row & 7) of that row
-    const int srow = lane >> 3;
-    unsigned voffA = (unsigned)srow * (unsigned)p.lda * ESZ + (unsigned)(((lane & 7) ^ srow) << 4);
-    unsigned voffB = (unsigned)srow * (unsigned)p.ldw * ESZ + (unsigned)(((lane & 7) ^ srow) << 4);
+    unsigned voffA = gf_a4_voff<ESZ>(lane, (unsigned)p.lda), voffB = gf_a4_voff<ESZ>(lane, (unsigned)p.ldw);
     // L2 warm-up loads (one line per lane): lane l = row l of this wave's 64 staging rows
     unsigned pfA = (unsigned)lane * (unsigned)p.lda * ESZ, pfB = (unsigned)lane * (unsigned)p.ldw * ESZ;
     const unsigned long baseA = (unsigned long)((const char*)p.A + (long)m0 * p.lda * ESZ);
@@ -829,6 +760,7 @@ __global__ __launch_bounds__(A4_THREADS, 1) void gemm_a4_kernel(const GemmArgs p
     const unsigned kb = (unsigned)p.K * ESZ;
 
     // ---- fragment read addresses: (row, chunk) at row * 128 + ((chunk ^ (row & 7)) << 4); sub-step ks reads chunk 4 ks + fq
+    // (spelled out here and in conv_a4_kernel: every helper tried for them changed the instruction stream, see gf_mfma_frame.h)
     const int frow = lane & 15, fq = lane >> 4, sw = frow & 7;
     const unsigned lbase = (unsigned)(unsigned long)lds;
     unsigned rdA0 = lbase + (unsigned)((wm * 128 + frow) * 128 + (((0 + fq) ^ sw) << 4));
@@ -900,14 +832,14 @@ __global__ __launch_bounds__(A4_THREADS, 1) void gemm_a4_kernel(const GemmArgs p
             for (int r = 0; r < 4; ++r) csc[j][r] = (n + r < p.wrows) ? p.row_scale[n + r] : 0.f;
         }
     }
-    a4_static_for<0, 8>([&](auto j_c) {
+    gf_static_for<0, 8>([&](auto j_c) {
         constexpr int j = decltype(j_c)::value;
         const int n = n0 + wn * 128 + j * 16 + fq * 4;
         const float bv[4] = {bf2f(bpre[j][0]), bf2f(bpre[j][1]), bf2f(bpre[j][2]), bf2f(bpre[j][3])};   // zeros where there is no bias
-        a4_static_for<0, 8>([&](auto i_c) {
+        gf_static_for<0, 8>([&](auto i_c) {
             constexpr int i = decltype(i_c)::value;
             constexpr int A0 = (i * 8 + j) * 4;
-            float y[4] = {a4_acc<A0>(), a4_acc<A0 + 1>(), a4_acc<A0 + 2>(), a4_acc<A0 + 3>()};
+            float y[4] = {gf_agpr_read<A0>(), gf_agpr_read<A0 + 1>(), gf_agpr_read<A0 + 2>(), gf_agpr_read<A0 + 3>()};
             if constexpr (FP8 && EPI != GF_EPI_VT32) {   // x scale_a of the row, + bias: the same expression as the 8-wave fp8 kernel (gemm_kernel<EPI, true>)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) y[r] = y[r] * rsc[i] + bv[r];
@@ -995,18 +927,8 @@ int launch_gemm_a4(const GemmArgs& a0, hipStream_t stream) {
         const int g = gf_options().a4_group_m.load(std::memory_order_relaxed);
         a.group_m = g > 0 ? g : (a.K * (FP8 ? 1 : 2) >= 16384 ? 4 : GROUP_M);   // by the K loop's length in bytes per row
     }
-    static GfDeviceOnce once;
-    hipError_t e = gf_once_per_device(once, [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_a4_kernel<EPI, FP8>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS);
-    });
-    if (e != hipSuccess) {
-        gf_set_error("gf_gemm: hipFuncSetAttribute(%d B LDS) failed: %s", GEMM_LDS, hipGetErrorString(e));
-        return GF_ERR_LAUNCH;
-    }
-    hipLaunchKernelGGL((gemm_a4_kernel<EPI, FP8>), dim3((unsigned)(a.tiles_m * a.tiles_n)), dim3(A4_THREADS), GEMM_LDS, stream, a);
-    GF_CHECK_LAUNCH(FP8 ? "gf_gemm_fp8" : "gf_gemm_bf16");
-    return GF_OK;
+    return gf_launch_lds<gemm_a4_kernel<EPI, FP8>>("gf_gemm", GF_ATTR_MSG_BYTES, FP8 ? "gf_gemm_fp8" : "gf_gemm_bf16", dim3((unsigned)(a.tiles_m * a.tiles_n)),
+                                                   dim3(A4_THREADS), GEMM_LDS, stream, a);
 }
 
 template <int EPI, bool FP8>
@@ -1024,41 +946,16 @@ int launch_gemm(const GemmArgs& a, hipStream_t stream) {
     }
     // small M: bf16 runs the phased 8-wave kernel, fp8 the one-barrier-per-K-tile 8-wave kernel (at 254 VGPRs the phased fp8
     // variant measured 10-15 % slower)
-    static GfDeviceOnce once;   // per instantiation
-    hipError_t e = gf_once_per_device(once, [] {
-        const void* fn;
-        if constexpr (FP8) fn = reinterpret_cast<const void*>(gemm_kernel<EPI, true>);
-        else fn = reinterpret_cast<const void*>(gemm_ph_kernel<EPI, false>);
-        return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS);
-    });
-    if (e != hipSuccess) {
-        gf_set_error("gf_gemm: hipFuncSetAttribute(%d B LDS) failed: %s", GEMM_LDS, hipGetErrorString(e));
-        return GF_ERR_LAUNCH;
-    }
-    if constexpr (FP8)
-        hipLaunchKernelGGL((gemm_kernel<EPI, true>), dim3((unsigned)(a.tiles_m * a.tiles_n)), dim3(GEMM_THREADS), GEMM_LDS, stream, a);
-    else
-        hipLaunchKernelGGL((gemm_ph_kernel<EPI, false>), dim3((unsigned)(a.tiles_m * a.tiles_n)), dim3(GEMM_THREADS), GEMM_LDS,
-                           stream, a);
-    GF_CHECK_LAUNCH(FP8 ? "gf_gemm_fp8" : "gf_gemm_bf16");
-    return GF_OK;
+    const dim3 grid((unsigned)(a.tiles_m * a.tiles_n)), block(GEMM_THREADS);
+    if constexpr (FP8) return gf_launch_lds<gemm_kernel<EPI, true>>("gf_gemm", GF_ATTR_MSG_BYTES, "gf_gemm_fp8", grid, block, GEMM_LDS, stream, a);
+    else return gf_launch_lds<gemm_ph_kernel<EPI, false>>("gf_gemm", GF_ATTR_MSG_BYTES, "gf_gemm_bf16", grid, block, GEMM_LDS, stream, a);
 }
 
 template <int EPI, int NB, int CONV>
 int launch_conv(const GemmArgs& a, hipStream_t stream, int batch = 1) {
-    static GfDeviceOnce once;
-    hipError_t e = gf_once_per_device(once, [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_ph_kernel<EPI, false, CONV, NB>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS);
-    });
-    if (e != hipSuccess) {
-        gf_set_error("gf_conv3d: hipFuncSetAttribute(%d B LDS) failed: %s", GEMM_LDS, hipGetErrorString(e));
-        return GF_ERR_LAUNCH;
-    }
-    hipLaunchKernelGGL((gemm_ph_kernel<EPI, false, CONV, NB>), dim3((unsigned)(a.tiles_m * a.tiles_n), (unsigned)batch), dim3(GEMM_THREADS),
-                       GEMM_LDS, stream, a);
-    GF_CHECK_LAUNCH("gf_conv3d_bf16");
-    return GF_OK;
+    return gf_launch_lds<gemm_ph_kernel<EPI, false, CONV, NB>>("gf_conv3d", GF_ATTR_MSG_BYTES, "gf_conv3d_bf16",
+                                                               dim3((unsigned)(a.tiles_m * a.tiles_n), (unsigned)batch), dim3(GEMM_THREADS),
+                                                               GEMM_LDS, stream, a);
 }
 
 // 256 zero bytes per device: where the convolution's padding taps and K-padding columns are fetched from.  A __device__

@@ -22,7 +22,7 @@
 //        jj of channel 16 db + r is the same key: gf_sage_quant_vt stores every 128-key slice in that order (position 32 g + jj).
 //   Row sums l on the matrix pipe: a ninth channel block whose A fragment is e4m3 1.0 in row 0.
 //   K~ and V^T tiles (16 KiB each) arrive by LDS-DMA into a 2-deep ring; the blockIdx map is kernel 3's XCD-aware one.
-#include "gf_common.h"
+#include "gf_mfma_frame.h"
 
 namespace {
 
@@ -242,19 +242,8 @@ __global__ __launch_bounds__(64 * SAGE_NW, 2) void sage_attn_fwd_kernel(const Sa
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 15, g = lane >> 4;
-    int head, qb0;
-    {
-        const int pid = blockIdx.x;
-        // XCD-aware (kernel 3's map): the CUs of one XCD walk the query blocks of ONE head, its K~ / V^T stream shared in their L2
-        if ((p.heads & 7) == 0) {
-            const int xcd = pid & 7, idx = pid >> 3;
-            head = xcd + 8 * (idx / p.n_qblocks);
-            qb0 = idx % p.n_qblocks;
-        } else {
-            head = pid / p.n_qblocks;
-            qb0 = pid % p.n_qblocks;
-        }
-    }
+    int head, qb0;   // XCD-aware (kernel 3's map): the CUs of one XCD walk the query blocks of ONE head, its K~ / V^T stream shared in their L2
+    gf_xcd_head_block(blockIdx.x, p.heads, p.n_qblocks, head, qb0);
     const int q0 = qb0 * SAGE_QB + wave * 32;
 
     // Q codes: qf[qb][ks] = bytes 64 ks + 16 g .. +16 of query q0 + 16 qb + r
@@ -563,14 +552,6 @@ extern "C" GF_API int gf_sage_attn_fwd(const void* q8, const float* q_scale, con
     // the row maximum is taken on the int32 dots and dequantised once: that is the maximum of the scores only for w = s_q s_k c >= 0
     GF_CHECK_ARG(scale > 0.f && scale < INFINITY, "gf_sage_attn_fwd: the softmax scale must be positive and finite (got %g)", (double)scale);
     if (q_len == 0) return GF_OK;
-    static GfDeviceOnce once;
-    hipError_t e = gf_once_per_device(once, [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(sage_attn_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, SAGE_LDS);
-    });
-    if (e != hipSuccess) {
-        gf_set_error("gf_sage_attn_fwd: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-        return GF_ERR_LAUNCH;
-    }
     SageArgs a;
     a.q8 = (const signed char*)q8;
     a.q_scale = q_scale;
@@ -587,9 +568,8 @@ extern "C" GF_API int gf_sage_attn_fwd(const void* q8, const float* q_scale, con
     a.n_qblocks = (int)((q_len + SAGE_QB - 1) / SAGE_QB);
     a.nqs = (int)((q_len + SAGE_QBLK - 1) / SAGE_QBLK);
     a.c = scale * 1.4426950408889634f;   // the factor kernel 3 uses (gf_attention.hip: scale_log2e)
-    hipLaunchKernelGGL(sage_attn_fwd_kernel, dim3((unsigned)(a.n_qblocks * a.heads)), dim3(64 * SAGE_NW), SAGE_LDS, (hipStream_t)stream, a);
-    GF_CHECK_LAUNCH("gf_sage_attn_fwd");
-    return GF_OK;
+    return gf_launch_lds<sage_attn_fwd_kernel>("gf_sage_attn_fwd", GF_ATTR_MSG_PLAIN, "gf_sage_attn_fwd", dim3((unsigned)(a.n_qblocks * a.heads)), dim3(64 * SAGE_NW),
+                                               SAGE_LDS, (hipStream_t)stream, a);
 }
 
 extern "C" GF_API int gf_sage_attn(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, int vt_in, void* o,

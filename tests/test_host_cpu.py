@@ -362,6 +362,39 @@ def test_generated_k_loops_are_what_their_generators_emit(tmp_path):
         assert out.read_bytes() == open(os.path.join(ROOT, "goal_force_amd", "csrc", inc), "rb").read(), f"{inc} is not what tools/{gen} emits"
 
 
+def test_k_loop_replay_accepts_the_shipped_loops_and_refuses_broken_ones(monkeypatch):
+    """tools/a4_loop.check replays the slot plan of the bf16 GEMM loop and of the convolution loop (fragment lifetimes, SCC chains, piece
+    and read counts).  It accepts the two shipped loops; it refuses a sub-step-0 fragment loaded while the first half's MFMAs still
+    read it (the last A fragment v[156:159], read through slot 63 of the GEMM's 128 / 47 of the convolution's 96) and an SCC writer
+    between the loop-closing compare and the branch."""
+    for k in [k for k in os.environ if k.startswith(("A4", "CONV_A4"))]:
+        monkeypatch.delenv(k)
+    monkeypatch.syspath_prepend(os.path.join(ROOT, "tools"))
+    import a4_loop
+    import gen_conv_a4
+    import gen_gemm_a4
+    for lines, shape, last_reader in ((gen_gemm_a4.gen(), (8, 8, 8, 8), 63), (gen_conv_a4.gen()[0], (8, 6, 8, 6), 47)):
+        inc = "gf_gemm_a4_loop.inc" if shape[1] == 8 else "gf_conv_a4_loop.inc"
+        shipped = open(os.path.join(ROOT, "goal_force_amd", "csrc", inc)).read()
+        assert all(f'"{l}\\n\\t"' in shipped for l in lines), f"{inc} is not this loop"
+        a4_loop.check(lines, *shape)
+        top = lines.index("1:")
+        mfmas = [l for l in lines[top:] if l.startswith("v_mfma")]
+        assert max(n for n, l in enumerate(mfmas[:len(mfmas) // 2]) if "v[156:159]" in l) == last_reader
+        moved = list(lines)
+        at = max(n for n, l in enumerate(moved) if l.startswith("ds_read_b128 v[156:159], "))
+        assert at > top and moved[top + 1].startswith("v_mfma")
+        moved.insert(top + 2, moved.pop(at))               # directly behind the loop's first MFMA
+        with pytest.raises(AssertionError, match="overwritten while the first half still reads it"):
+            a4_loop.check(moved, *shape)
+        clobbered = list(lines)
+        close = max(n for n, l in enumerate(clobbered) if l.startswith("s_cmp_eq_u32"))
+        assert close < clobbered.index("s_cbranch_scc0 1b")
+        clobbered.insert(close + 1, "s_add_u32 s58, s58, 1")
+        with pytest.raises(AssertionError, match="the loop-closing compare is not the last SCC writer before the branch"):
+            a4_loop.check(clobbered, *shape)
+
+
 def test_experiment_patches_still_apply_to_the_product_sources():
     """tools/patches/*_experiments.patch hold the kernels and diagnostic builds that left the product sources (attention kernel 1, the
     sl GEMMs, the first backward kernels, the env-variable selectors).  They are diffs against the CURRENT product files: an edit to

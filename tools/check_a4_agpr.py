@@ -26,13 +26,13 @@ AGPR = re.compile(r"\ba\d+\b|\ba\[(?:0x[0-9a-f]+|\d+)(?::\d+)?\]")
 SAVED = os.path.join(ROOT, "build", "csrc", "gf_gemm-hip-amdgcn-amd-amdhsa-gfx950.s")
 # (source, saved assembly, files it depends on, kernel name, the accumulators its loop leaves behind)
 UNITS = [
-    (SRC, SAVED, ("gf_gemm_a4_loop.inc", "gf_gemm_a4f8_loop.inc", "gf_common.h"), "gemm_a4_kernel", set(range(256))),
+    (SRC, SAVED, ("gf_gemm_a4_loop.inc", "gf_gemm_a4f8_loop.inc", "gf_common.h", "gf_mfma_frame.h"), "gemm_a4_kernel", set(range(256))),
     (os.path.join(ROOT, "goal_force_amd", "csrc", "gf_conv_a4.hip"), os.path.join(ROOT, "build", "csrc", "gf_conv_a4-hip-amdgcn-amd-amdhsa-gfx950.s"),
-     ("gf_conv_a4_loop.inc", "gf_common.h"), "conv_a4_kernel", {(i * 8 + j) * 4 + r for i in range(8) for j in range(6) for r in range(4)}),
+     ("gf_conv_a4_loop.inc", "gf_common.h", "gf_mfma_frame.h"), "conv_a4_kernel", {(i * 8 + j) * 4 + r for i in range(8) for j in range(6) for r in range(4)}),
 ]
 
 
-def device_asm(src=SRC, saved=SAVED, dep_names=("gf_gemm_a4_loop.inc", "gf_gemm_a4f8_loop.inc", "gf_common.h")):
+def device_asm(src=SRC, saved=SAVED, dep_names=("gf_gemm_a4_loop.inc", "gf_gemm_a4f8_loop.inc", "gf_common.h", "gf_mfma_frame.h")):
     deps = [src] + [os.path.join(ROOT, "goal_force_amd", "csrc", f) for f in dep_names]
     if os.path.exists(saved) and all(os.path.getmtime(saved) >= os.path.getmtime(d) for d in deps):
         return open(saved).read(), saved

@@ -13,7 +13,7 @@ for v in "${@:-ds4_w64_r2:4:64:2 ds4_w64_r1:4:64:1 ds4_w70_r1:4:70:1 ds5_w70_r1:
     IFS=: read name ds w r <<< "$spec"
     d=build/variants/conv_$name
     mkdir -p $d
-    cp goal_force_amd/csrc/gf_conv_a4.hip goal_force_amd/csrc/gf_common.h $d/
+    cp goal_force_amd/csrc/gf_conv_a4.hip goal_force_amd/csrc/gf_common.h goal_force_amd/csrc/gf_mfma_frame.h $d/
     CONV_A4_DS=$ds CONV_A4_WAIT=$w CONV_A4_RDSTEP=$r CONV_A4_OUT=$d/gf_conv_a4_loop.inc python3 tools/gen_conv_a4.py > $d/gen.log
     /opt/rocm/bin/hipcc $F -I$d -c $d/gf_conv_a4.hip -o $d/gf_conv_a4.o 2> $d/cc.log
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $d/libgoalforce_hip.so $OBJS $d/gf_conv_a4.o

@@ -55,17 +55,14 @@ Measured and NOT kept (same box, one process, tools/gemm_ab.py; logs profiles/r0
 """
 import os
 
+import a4_loop
+from a4_loop import A_K0, B_K0, A_K1, B_K1, SRD_A, SRD_B, SOFF_A, SOFF_B, S_WR, STAGE, B_TILE, rd
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.path.join(ROOT, "goal_force_amd", "csrc", "gf_gemm_a4_loop.inc")
 
-# ---- register plan -------------------------------------------------------------------------------------------------
-A_K0, B_K0, A_K1, B_K1 = 128, 160, 192, 224          # fragment i of a set: v[base + 4 i : base + 4 i + 3]
-SRD_A, SRD_B = 60, 64                                 # s[60:63], s[64:67]
-SOFF_A, SOFF_B = 36, 44                               # s[36:43], s[44:51]: row-group offsets of this wave's 8 pieces
-S_M0SAVE, S_CNT, S_WR, S_NRA, S_NRB = 52, 53, 54, 56, 57
+NI, NJ, PA, PB = 8, 8, 8, 8                           # a wave = 128 x 128 of C; 256-row A and W tiles = 8 pieces each per wave
 S_POS, S_STEP, S_NK, S_WRAP = 58, 59, 68, 69          # staged K tile position (wraps at nk), voffset step of the next advance
-STAGE = 65536
-B_TILE = 32768
 CLOBBER_S = list(range(36, 60)) + list(range(60, 70))
 
 
@@ -84,12 +81,15 @@ WAIT_SLOT = int(os.environ.get("A4_WAIT_SLOT", "88"))
 # gf_gemm.hip GF_A4_ROWMAP=1: the four waves walk down the tile together; +0.5 / +1.1 / +1.3 % on D->D / D->F / F->D against each
 # wave staging its own 64 consecutive rows, 0x400 with GF_A4_ROWMAP=0)
 PIECE_STEP = int(os.environ.get("A4_PIECE_STEP", "0x1000"), 0)
-FRAG_STEP = 2048                                      # LDS bytes between the fragments of consecutive 16-row blocks
 M0_LATE = int(os.environ.get("A4_M0_LATE", "1"))      # MFMA slots between an LDS-DMA piece and the M0 step that follows it (0: right behind it)
 B_FIRST = os.environ.get("A4_B_FIRST", "0") == "1"    # experiment: after the wait read B(t+1) sub-step 0 first, A rows 3..7 early in the next iteration
 MERGE_B12 = False     # True: one barrier (instead of two) between the k-sub-step-1 reads and the staging of tile t+2 — measured 4 % SLOWER
 PF_TILES = 6          # L2 warm-up distance beyond the staged tile (K tiles); the instruction offset field holds <= 31
 V_DUMMY = 126         # v[126:127]: destinations of the warm-up loads (never read)
+J_OUTER = os.environ.get("A4_J_OUTER", "0") == "1"    # experiment: the MFMA's FIRST source operand (the W fragment) constant over 8 MFMAs instead of the second
+R1 = int(os.environ.get("A4_RD1_STRIDE", "1"))        # MFMA slots between the sub-step-1 reads of A (1 shipped: B1 at slot 11; 2: 19)
+DS = int(os.environ.get("A4_DMA_STRIDE", "6"))        # MFMA slots between staging pieces (6 shipped: see the module docstring)
+REREAD = tuple(A_K0 + 4 * i for i in range(3, 8)) if B_FIRST else ()
 
 
 def warm(which):
@@ -100,104 +100,20 @@ def warm(which):
     return f"buffer_load_dword v{V_DUMMY + which}, {voff}, s[{srd}:{srd + 3}], s{soff} offen offset:{PF_TILES * 128}"
 
 
-def v4(base, i):
-    return f"v[{base + 4 * i}:{base + 4 * i + 3}]"
-
-
-def acc(i, j):
-    b = (i * 8 + j) * 4
-    return f"a[{b}:{b + 3}]"
-
-
-J_OUTER = os.environ.get("A4_J_OUTER", "0") == "1"    # experiment: the MFMA's FIRST source operand (the W fragment) constant over 8 MFMAs instead of the second
-
-
-def mfma(half, g):
-    i, j = (g & 7, g >> 3) if J_OUTER else (g >> 3, g & 7)
-    a, b = (A_K0, B_K0) if half == 0 else (A_K1, B_K1)
-    return f"v_mfma_f32_16x16x32_bf16 {acc(i, j)}, {v4(b, j)}, {v4(a, i)}, {acc(i, j)}"
-
-
-def dma(which, p, back_to_back=False):
-    """One 1-KiB piece + the M0 step to the next piece's LDS address (an M0 write needs one wait state before the next LDS-DMA:
-    in the loop the next piece is several MFMAs away, in the prologue an s_nop pads it)."""
-    srd, soff, voff = (SRD_A, SOFF_A, "%[voffA]") if which == 0 else (SRD_B, SOFF_B, "%[voffB]")
-    return [f"buffer_load_dwordx4 {voff}, s[{srd}:{srd + 3}], s{soff + p} offen lds", f"s_add_u32 m0, m0, {PIECE_STEP:#x}"] + \
-        (["s_nop 0"] if back_to_back else [])
-
-
-def dma_tile(fill=None):
-    """16 pieces of one tile (prologue): back to back, or — `fill`, 16 lists of instructions — each followed by its share of other
-    work (tile 1 is staged between the zeroing of the accumulators: nothing waits for it yet, and a burst of LDS-DMA instructions
-    is expensive, see the module docstring)."""
-    out = [f"s_mov_b32 m0, s{S_WR}", "s_nop 0"]
-    for p in range(8):
-        out += dma(0, p, fill is None) + ([] if fill is None else fill[p])
-    out += [f"s_add_u32 m0, s{S_WR}, {B_TILE}", "s_nop 0"]
-    for p in range(8):
-        out += dma(1, p, fill is None) + ([] if fill is None else fill[8 + p])
-    out += advance_k() + ADVANCE_V
-    return out
-
-
-def rd(dst_base, i, addr, extra=0):
-    off = i * FRAG_STEP + extra
-    return f"ds_read_b128 {v4(dst_base, i)}, {addr}" + (f" offset:{off}" if off else "")
-
-
 def gen(whatif=0):
     """whatif (timing-only builds, wrong results): 1 = no barriers / counted waits in the loop, 2 = the K position never advances
     (every tile re-reads the first one: all staging hits L2), 4 = no staging instructions in the loop."""
-    L = []
-    # ---- prologue ------------------------------------------------------------------------------------------------------
-    L += [f"s_mov_b32 s{S_M0SAVE}, m0"]
-    L += [f"s_mov_b32 s{SRD_A}, %[aLo]", f"s_mov_b32 s{SRD_A + 1}, %[aHi]", f"s_mov_b32 s{SRD_A + 2}, %[nrA]",
-          f"s_mov_b32 s{SRD_A + 3}, 0x00020000",
-          f"s_mov_b32 s{SRD_B}, %[bLo]", f"s_mov_b32 s{SRD_B + 1}, %[bHi]", f"s_mov_b32 s{SRD_B + 2}, %[nrB]",
-          f"s_mov_b32 s{SRD_B + 3}, 0x00020000",
-          f"s_mov_b32 s{S_NRA}, %[nrA]", f"s_mov_b32 s{S_NRB}, %[nrB]", f"s_mov_b32 s{S_CNT}, %[nk]",
-          f"s_mov_b32 s{S_WR}, %[ldsW]",
-          # staggered start: this tile's K loop begins at K tile k0 and wraps (the sum over k is rotated, not changed)
-          f"s_mov_b32 s{S_NK}, %[nk]", f"s_mov_b32 s{S_POS}, %[k0]", f"s_sub_u32 s{S_WRAP}, 128, %[kb]",
-          f"s_lshl_b32 s{S_STEP}, %[k0], 7", "s_nop 0",
-          f"v_add_u32 %[voffA], s{S_STEP}, %[voffA]", f"v_add_u32 %[voffB], s{S_STEP}, %[voffB]",
-          f"v_add_u32 %[pfA], s{S_STEP}, %[pfA]", f"v_add_u32 %[pfB], s{S_STEP}, %[pfB]"]
-    L += [f"s_mov_b32 s{SOFF_A}, %[soA]", f"s_mov_b32 s{SOFF_B}, %[soB]"]
-    for p in range(1, 8):
-        L += [f"s_add_u32 s{SOFF_A + p}, s{SOFF_A + p - 1}, %[stA]", f"s_add_u32 s{SOFF_B + p}, s{SOFF_B + p - 1}, %[stB]"]
-    L += dma_tile()                                                   # tile 0 -> stage 0
-    L += [f"s_xor_b32 s{S_WR}, s{S_WR}, {STAGE}",
-          f"s_cmp_gt_u32 s{S_CNT}, 1", f"s_cselect_b32 s{SRD_A + 2}, s{S_NRA}, 0", f"s_cselect_b32 s{SRD_B + 2}, s{S_NRB}, 0",
-          "s_nop 1"]
-    if os.environ.get("A4_PROLOGUE_DENSE", "0") == "1":               # the round's first version: 32 pieces back to back, then the zeroing
-        L += dma_tile()                                               # tile 1 -> stage 1 (zeros past K)
-        L += [f"s_xor_b32 s{S_WR}, s{S_WR}, {STAGE}"]
-        for r in range(256):
-            L.append(f"v_accvgpr_write_b32 a{r}, 0")
-    else:
-        # tile 1 -> stage 1 (zeros past K), one piece per 16 accumulator registers zeroed (under the latency of tile 0)
-        L += dma_tile([[f"v_accvgpr_write_b32 a{16 * q + r}, 0" for r in range(16)] for q in range(16)])
-        L += [f"s_xor_b32 s{S_WR}, s{S_WR}, {STAGE}"]
-    L += ["s_waitcnt vmcnt(16)", "s_barrier"]
-    for i in range(8):
-        L.append(rd(A_K0, i, "%[rdA0]"))
-    for j in range(8):
-        L.append(rd(B_K0, j, "%[rdB0]"))
-    L += ["s_waitcnt lgkmcnt(0)"]
-
-    # ---- the loop ------------------------------------------------------------------------------------------------------
-    ev = {}                      # MFMA slot (0..127) -> instructions issued right after it
-
-    def at(slot, *ins):
-        ev.setdefault(slot, []).extend(ins)
-
-    # tile t+2 exists iff remaining > 2
-    at(0, f"s_cmp_gt_u32 s{S_CNT}, 2", f"s_cselect_b32 s{SRD_A + 2}, s{S_NRA}, 0")
-    at(1, f"s_cselect_b32 s{SRD_B + 2}, s{S_NRB}, 0")
-    last_piece, n_before = 70, 16
+    F = a4_loop.Loop(NI, NJ, PA, PB, advance_k() + ADVANCE_V, PIECE_STEP, J_OUTER)
+    at = F.at
+    # staggered start: this tile's K loop begins at K tile k0 and wraps (the sum over k is rotated, not changed)
+    L = F.prologue([f"s_mov_b32 s{S_NK}, %[nk]", f"s_mov_b32 s{S_POS}, %[k0]", f"s_sub_u32 s{S_WRAP}, 128, %[kb]",
+                    f"s_lshl_b32 s{S_STEP}, %[k0], 7", "s_nop 0"] + ADVANCE_V,
+                   soff_interleaved=True, dense=os.environ.get("A4_PROLOGUE_DENSE", "0") == "1")   # dense: the round's first version
     if MERGE_B12:
         # ONE barrier for both operands: all 16 k-sub-step-1 reads first, then the 16 pieces of tile t+2.  (Three barriers per
         # iteration cost the F->D shape 11 % in waves waiting for each other: tools/gemm_a4_whatif.py, whatif 128.)
+        at(0, f"s_cmp_gt_u32 s{a4_loop.S_CNT}, 2", f"s_cselect_b32 s{SRD_A + 2}, s{a4_loop.S_NRA}, 0")
+        at(1, f"s_cselect_b32 s{SRD_B + 2}, s{a4_loop.S_NRB}, 0")
         for i in range(8):
             at(2 * i, rd(A_K1, i, "%[rdA1]"))
             at(16 + 2 * i, rd(B_K1, i, "%[rdB1]"))
@@ -205,42 +121,16 @@ def gen(whatif=0):
         at(34, "s_waitcnt lgkmcnt(0)")
         at(35, "s_barrier")
         for p in range(8):
-            at(36 + 2 * p, *dma(0, p))
+            at(36 + 2 * p, *F.dma(0, p))
         at(52, f"s_add_u32 m0, s{S_WR}, {B_TILE}")
         for p in range(8):
-            at(54 + 2 * p, *dma(1, p))
+            at(54 + 2 * p, *F.dma(1, p))
+        last_piece, n_before = 70, 16
     else:
-        R1 = int(os.environ.get("A4_RD1_STRIDE", "1"))       # MFMA slots between the sub-step-1 reads of A (1 shipped: B1 at slot 11)
-        b1 = 8 * R1 + 3                                       # B1: behind the last of them (19 at R1 = 2)
-        for i in range(8):
-            at(R1 * i, rd(A_K1, i, "%[rdA1]"))
-        at(b1 - 2, f"s_mov_b32 m0, s{S_WR}")
-        at(b1 - 1, "s_waitcnt lgkmcnt(0)")
-        at(b1, "s_barrier")
-        DS = int(os.environ.get("A4_DMA_STRIDE", "6"))        # MFMA slots between staging pieces (6 shipped: see the module docstring)
-        b2 = b1 + 1 + DS * 7 + 1 + 5                           # B2: behind the last sub-step-1 read of B (47 at R1 = 2, DS = 3)
-        a_slots = [b1 + 1 + DS * p for p in range(8)]
-        b_slots = [b2 + 1 + DS * p for p in range(8)]
-        b_slots = [x + 2 if x in (WAIT_SLOT, WAIT_SLOT + 1) else x for x in b_slots]    # not between the counted wait and its barrier
-        for p in range(8):
-            at(a_slots[p], dma(0, p)[0])
-            at(a_slots[p] + 1, rd(B_K1, p, "%[rdB1]"))
-            if p < 7:
-                at(a_slots[p] + M0_LATE, dma(0, p)[1])        # the M0 step: not glued to the piece that still has to read M0
-        at(b2 - 2, f"s_add_u32 m0, s{S_WR}, {B_TILE}")
-        at(b2 - 1, "s_waitcnt lgkmcnt(0)")
-        at(b2, "s_barrier")
-        for p in range(8):
-            at(b_slots[p], dma(1, p)[0])
-            if p < 7:
-                at(b_slots[p] + M0_LATE, dma(1, p)[1])
-        last_piece = b_slots[7]
-        # pieces of this iteration that are issued before the counted wait: everything older than them (= all of tile t+1, including
-        # the pieces the previous iteration issued behind ITS wait) has landed once vmcnt has dropped to their number
-        n_before = sum(1 for x in a_slots + b_slots if x < WAIT_SLOT)
-        assert last_piece <= 119 and a_slots[7] < WAIT_SLOT, "staging must end before the loop counter's scalar compare"
-    at(70, "v_xor_b32 %[rdA0], 0x10000, %[rdA0]", "v_xor_b32 %[rdA1], 0x10000, %[rdA1]")
-    at(71, "v_xor_b32 %[rdB0], 0x10000, %[rdB0]", "v_xor_b32 %[rdB1], 0x10000, %[rdB1]")
+        plan = F.plan_staging(R1, DS, M0_LATE, WAIT_SLOT, lambda a_slots: a_slots[-1] + 6)   # B2 at 60; 47 at R1 = 2, DS = 3
+        last_piece, n_before = plan["b_slots"][-1], plan["n_before"]
+        assert last_piece <= 119, "staging must end before the loop counter's scalar compare"
+    F.plan_toggle_reads(70)
     at(72, f"s_xor_b32 s{S_WR}, s{S_WR}, {STAGE}")
     # the wait for tile t+1 sits as late as the 16 fragment reads behind it allow: every slot it moves back is lead time for
     # the LDS-DMA (two LDS stages leave it ~1.3 iterations between issue and this wait)
@@ -258,63 +148,40 @@ def gen(whatif=0):
             at(1 + 2 * n, rd(A_K0, i, "%[rdA0]"))
         # (the lgkmcnt(0) before barrier B1 at slot 18 covers them: their first use is slot 24)
     else:
-        for i in range(8):
-            at(WAIT_SLOT + 2 + 2 * i, rd(A_K0, i, "%[rdA0]"))
-        for j in range(8):
-            at(WAIT_SLOT + 18 + 2 * j, rd(B_K0, j, "%[rdB0]"))
+        F.plan_next_reads(WAIT_SLOT + 2, 2)
     adv = max(76, (last_piece + 1) if not MERGE_B12 else 76)   # the staging position moves on only behind the iteration's last piece
     at(adv, *advance_k()[:2])
     at(adv + 1, *advance_k()[2:])
     at(adv + 4, *ADVANCE_V)
-    at(124, f"s_sub_u32 s{S_CNT}, s{S_CNT}, 1")
-    at(125, f"s_cmp_eq_u32 s{S_CNT}, 0")
-    at(126, "s_waitcnt lgkmcnt(0)")
-    L.append("1:")
-    for s in range(128):
-        L.append(mfma(s >> 6, s & 63))
-        for ins in ev.get(s, []):
-            if (whatif & 1) and (ins == "s_barrier" or ins.startswith("s_waitcnt vmcnt")):
-                continue
-            if (whatif & 64) and ins.startswith("s_waitcnt vmcnt"):
-                continue
-            if (whatif & 128) and ins == "s_barrier":
-                continue
-            if (whatif & 2) and ins.startswith("v_add_u32 %[voff"):
-                continue
-            if (whatif & 4) and ins.startswith("buffer_load_dwordx4"):
-                continue
-            L.append(ins)
-    L += ["s_cbranch_scc0 1b"]
-    # ---- drain: the last two iterations staged zero tiles; they must have landed (and every wave must be past its reads)
-    # before the epilogue reuses LDS.  MFMA results need 4 passes + margin before v_accvgpr_read.
-    L += ["s_waitcnt vmcnt(0)", "s_nop 7", "s_nop 7", f"s_mov_b32 m0, s{S_M0SAVE}", "s_barrier"]
+
+    def keep(ins):
+        if (whatif & 1) and (ins == "s_barrier" or ins.startswith("s_waitcnt vmcnt")):
+            return False
+        if (whatif & 64) and ins.startswith("s_waitcnt vmcnt"):
+            return False
+        if (whatif & 128) and ins == "s_barrier":
+            return False
+        if (whatif & 2) and ins.startswith("v_add_u32 %[voff"):
+            return False
+        return not ((whatif & 4) and ins.startswith("buffer_load_dwordx4"))
+
+    L += F.body(keep)
+    if not whatif:
+        a4_loop.check(L, NI, NJ, PA, PB, REREAD)
     return L
 
 
-def emit(name, lines):
-    n_mfma = sum(1 for l in lines if l.startswith("v_mfma"))
-    assert n_mfma == 128, n_mfma
-    body = "\n".join(f'    "{l}\\n\\t"' for l in lines)
-    vclob = ", ".join(f'"v{r}"' for r in range(V_DUMMY, 256))
-    aclob = ", ".join(f'"a{r}"' for r in range(256))
-    sclob = ", ".join(f'"s{r}"' for r in CLOBBER_S)
-    text = f"""// GENERATED by tools/gen_gemm_a4.py — do not edit.  The K loop of gemm_a4_kernel as one asm statement.
+HEADER = """// GENERATED by tools/gen_gemm_a4.py — do not edit.  The K loop of gemm_a4_kernel as one asm statement.
 // operands: voffA/voffB (per-lane source byte offsets, advanced by 128 per K tile), pfA/pfB (row-per-lane offsets of the L2
 // warm-up loads, advanced alike), rdA0/rdA1/rdB0/rdB1 (LDS fragment read
 // addresses of k-sub-steps 0/1, stage toggled by XOR 0x10000), aLo/aHi/nrA, bLo/bHi/nrB (tile row base + valid bytes),
 // soA/stA, soB/stB (this wave's first row-group offset and the 8-row stride, bytes), ldsW (this wave's LDS write base in
-// stage 0), nk (K tiles >= 1), k0 (first K tile of this workgroup's rotated K loop, < nk), kb (K in bytes).  Accumulators are left in a[0:255]: a[(i*8+j)*4 + r] = C[16 i + lane%16][16 j + 4 (lane/16) + r].
-#define {name}(voffA, voffB, pfA, pfB, rdA0, rdA1, rdB0, rdB1, aLo, aHi, nrA, bLo, bHi, nrB, soA, stA, soB, stB, ldsW, nk, k0, kb) \\
-    asm volatile( \\
-{body.replace(chr(10), " " + chr(92) + chr(10))} \\
-        : [voffA] "+v"(voffA), [voffB] "+v"(voffB), [pfA] "+v"(pfA), [pfB] "+v"(pfB), [rdA0] "+v"(rdA0), [rdA1] "+v"(rdA1), [rdB0] "+v"(rdB0), [rdB1] "+v"(rdB1) \\
-        : [aLo] "s"(aLo), [aHi] "s"(aHi), [nrA] "s"(nrA), [bLo] "s"(bLo), [bHi] "s"(bHi), [nrB] "s"(nrB), [soA] "s"(soA), \\
-          [stA] "s"(stA), [soB] "s"(soB), [stB] "s"(stB), [ldsW] "s"(ldsW), [nk] "s"(nk), [k0] "s"(k0), [kb] "s"(kb) \\
-        : "memory", "scc", "vcc", {sclob}, \\
-          {vclob}, \\
-          {aclob})
-"""
-    return text
+// stage 0), nk (K tiles >= 1), k0 (first K tile of this workgroup's rotated K loop, < nk), kb (K in bytes).  Accumulators are left in a[0:255]: a[(i*8+j)*4 + r] = C[16 i + lane%16][16 j + 4 (lane/16) + r]."""
+
+
+def emit(name, lines):
+    return a4_loop.emit(name, lines, 2 * NI * NJ, HEADER, ["voffA", "voffB", "pfA", "pfB", "rdA0", "rdA1", "rdB0", "rdB1"],
+                        a4_loop.srd_operands("nk", "k0", "kb"), CLOBBER_S, V_DUMMY)
 
 
 def main():
@@ -326,7 +193,7 @@ def main():
     out = os.environ.get("A4_OUT", OUT)
     with open(out, "w") as f:
         f.write(text)
-    print(f"wrote {out}")
+    print(f"wrote {out} (slot plan replayed)")
 
 
 if __name__ == "__main__":

@@ -38,6 +38,9 @@ last read of what it overwrites.
 import os
 import re
 
+import a4_loop
+from a4_loop import SRD_A, SRD_B, SOFF_A, SOFF_B, S_M0SAVE, S_CNT, S_WR, S_NRA, S_NRB, STAGE, B_TILE, FRAG_STEP, acc
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.path.join(ROOT, "goal_force_amd", "csrc", "gf_gemm_a4f8_loop.inc")
 
@@ -45,14 +48,8 @@ OUT = os.path.join(ROOT, "goal_force_amd", "csrc", "gf_gemm_a4f8_loop.inc")
 SET_A = (128, 160)                                    # the two A sets; fragment f of a set: v[base + 8 f : base + 8 f + 7]
 SET_B = (192, 224)                                    # B0 (W rows lo), B1 (W rows hi)
 V_RD = 120                                            # v[120:127]: fragment read addresses, (A c0, A c1, B c0, B c1) x stage
-SRD_A, SRD_B = 60, 64                                 # s[60:63], s[64:67]
-SOFF_A, SOFF_B = 36, 44                               # s[36:43], s[44:51]: row-group offsets of this wave's 8 pieces
-S_M0SAVE, S_CNT, S_WR, S_NRA, S_NRB = 52, 53, 54, 56, 57
-S_POS, S_STEP, S_NK, S_WRAP = 58, 59, 68, 69
-STAGE = 65536
-B_TILE = 32768
+S_POS, S_STEP, S_NK, S_WRAP = 58, 59, 68, 69          # the descriptors, piece offsets and loop state are a4_loop's register plan
 PIECE_STEP = 0x1000                                   # LDS bytes between a wave's consecutive pieces (GF_A4_ROWMAP = 1)
-FRAG_STEP = 2048                                      # LDS bytes between the fragments of consecutive 16-row blocks
 CLOBBER_S = list(range(36, 60)) + list(range(60, 70))
 LO_P, HI_P = (0, 1, 4, 5), (2, 3, 6, 7)               # pieces (32-row groups of the 256-row tile) of the waves' lo / hi 64-row halves
 
@@ -68,11 +65,6 @@ M0_LATE = 1                                           # MFMA slots between a pie
 
 def v8(base, f):
     return f"v[{base + 8 * f}:{base + 8 * f + 7}]"
-
-
-def acc(i, j):
-    b = (i * 8 + j) * 4
-    return f"a[{b}:{b + 3}]"
 
 
 def mfma(i, j, aset, bset):
@@ -380,31 +372,17 @@ def check(lines, nbodies=3):
     return True
 
 
-def emit(name, lines):
-    n_mfma = sum(1 for l in lines if l.startswith("v_mfma"))
-    assert n_mfma == (256 if BF16 else 128), n_mfma
-    body = "\n".join(f'    "{l}\\n\\t"' for l in lines)
-    vclob = ", ".join(f'"v{r}"' for r in range(V_RD - 1, 256))
-    aclob = ", ".join(f'"a{r}"' for r in range(256))
-    sclob = ", ".join(f'"s{r}"' for r in CLOBBER_S)
-    text = f"""// GENERATED by tools/gen_gemm_a4f8.py — do not edit.  The K loop of gemm_a4_kernel<EPI, FP8 = true> as one asm statement.
+HEADER = """// GENERATED by tools/gen_gemm_a4f8.py — do not edit.  The K loop of gemm_a4_kernel<EPI, FP8 = true> as one asm statement.
 // operands: voffA/voffB (per-lane source byte offsets, advanced by 128 per K tile), rdA0/rdA1/rdB0/rdB1 (LDS fragment read
 // addresses of chunk fq / chunk 4 + fq in stage 0), aLo/aHi/nrA, bLo/bHi/nrB (tile row base + valid bytes), soA/stA, soB/stB
 // (this wave's first row-group offset and the 32-row stride, bytes), ldsW (this wave's LDS write base in stage 0), nk (K tiles of
 // 128 bytes, >= 1), k0 (first K tile of this workgroup's rotated K loop, < nk), kb (K in bytes).
-// Accumulators are left in a[0:255]: a[(i*8+j)*4 + r] = C[16 i + lane%16][16 j + 4 (lane/16) + r].
-#define {name}(voffA, voffB, rdA0, rdA1, rdB0, rdB1, aLo, aHi, nrA, bLo, bHi, nrB, soA, stA, soB, stB, ldsW, nk, k0, kb) \\
-    asm volatile( \\
-{body.replace(chr(10), " " + chr(92) + chr(10))} \\
-        : [voffA] "+v"(voffA), [voffB] "+v"(voffB) \\
-        : [rdA0] "v"(rdA0), [rdA1] "v"(rdA1), [rdB0] "v"(rdB0), [rdB1] "v"(rdB1), \\
-          [aLo] "s"(aLo), [aHi] "s"(aHi), [nrA] "s"(nrA), [bLo] "s"(bLo), [bHi] "s"(bHi), [nrB] "s"(nrB), [soA] "s"(soA), \\
-          [stA] "s"(stA), [soB] "s"(soB), [stB] "s"(stB), [ldsW] "s"(ldsW), [nk] "s"(nk), [k0] "s"(k0), [kb] "s"(kb) \\
-        : "memory", "scc", "vcc", {sclob}, \\
-          {vclob}, \\
-          {aclob})
-"""
-    return text
+// Accumulators are left in a[0:255]: a[(i*8+j)*4 + r] = C[16 i + lane%16][16 j + 4 (lane/16) + r]."""
+
+
+def emit(name, lines):
+    return a4_loop.emit(name, lines, 256 if BF16 else 128, HEADER, ["voffA", "voffB"],
+                        [[(o, "v") for o in ("rdA0", "rdA1", "rdB0", "rdB1")]] + a4_loop.srd_operands("nk", "k0", "kb"), CLOBBER_S, V_RD - 1)
 
 
 def main():

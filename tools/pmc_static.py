@@ -14,10 +14,10 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-ATTN_SRC = ["gf_attention.hip", "gf_common.h"]
-GEMM_SRC = ["gf_gemm.hip", "gf_gemm_a4_loop.inc", "gf_gemm_a4f8_loop.inc", "gf_common.h"]
-CONV_A4_SRC = ["gf_conv_a4.hip", "gf_conv_a4_loop.inc", "gf_common.h"]
-CONV_C96_SRC = ["gf_conv_direct.hip", "gf_common.h"]
+ATTN_SRC = ["gf_attention.hip", "gf_common.h", "gf_mfma_frame.h"]
+GEMM_SRC = ["gf_gemm.hip", "gf_gemm_a4_loop.inc", "gf_gemm_a4f8_loop.inc", "gf_common.h", "gf_mfma_frame.h"]
+CONV_A4_SRC = ["gf_conv_a4.hip", "gf_conv_a4_loop.inc", "gf_common.h", "gf_mfma_frame.h"]
+CONV_C96_SRC = ["gf_conv_direct.hip", "gf_common.h", "gf_mfma_frame.h"]
 ENTRIES = {   # key -> (table tag, kernel-name substring, sources)
     "attn_self": ("attn", "flash_attn_fwd_kernel3", ATTN_SRC),
     "vae_conv_c192_n192_k33_m3": ("vae_l2", "conv_a4_kernel", CONV_A4_SRC),
