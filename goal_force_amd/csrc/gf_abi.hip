@@ -33,7 +33,7 @@ const OptionSlot kSlots[] = {
     {"prefer_8wave", &GfOptions::prefer_8wave, 0, 1, 0}, {"a4_stagger", &GfOptions::a4_stagger, 0, 1 << 20, 2},
     {"a4_group_m", &GfOptions::a4_group_m, 0, 64, 0},    {"conv_nb", &GfOptions::conv_nb, 0, 2, 0},
     {"conv_gather", &GfOptions::conv_gather, 0, 1, 0},   {"vae_rms3", &GfOptions::vae_rms3, 0, 1, 1},
-    {"conv_direct", &GfOptions::conv_direct, 0, 1, 1},
+    {"conv_direct", &GfOptions::conv_direct, 0, 1, 1},   {"attn_fixed_max", &GfOptions::attn_fixed_max, 0, 1, 1},
 };
 }  // namespace
 

@@ -53,6 +53,7 @@ struct AttnArgs {
     const int* tile_idx;   // ascending inside a row
     const int* head_map;   // [heads] or NULL (every head: map 0)
     int n_maps;
+    int* flags;            // kernel 3, fixed-max and repair modes: [heads * n_qblocks * 8], one word per wave (K3_FIXED writes, K3_REPAIR reads)
 };
 
 // ================================================================================================================
@@ -591,7 +592,20 @@ __device__ __forceinline__ void mfma16(f32x4& acc, const bf16x8& a, const bf16x8
 // wider chunk: a multi-dword load would read past the end of the last list.)
 // The dense instantiation compiles to the instruction stream it had before the flag existed (every sparse line hangs on the
 // compile-time flag; DESIGN §4.1c has the comparison).
-template <int NQ, bool SPARSE>
+//
+// MODE (gf_flash_attn_fwd_vt32_fm / _sparse_fm launch K3_FIXED, then K3_REPAIR on the same stream; the plain entry points K3_EXACT):
+//   K3_EXACT   the running maximum with the lazy rescale, as described above.
+//   K3_FIXED   the maximum stays at position 0's row maximum m0: the steady phases take no partial maxima, make no rescale
+//              decision and carry no pending rescale; the tail's softmax_plain skips them as well.  p = bf16(exp2(s - m0)) has
+//              the same relative precision at any magnitude (fp32 and bf16 share the exponent range), and m0 is a score of the
+//              row, so the row sum holds a term that is exactly 1: whatever underflows against it is negligible.  What can go
+//              wrong is overflow (a later score ~ 100 - 128 log2 units above m0), and it shows: a row sum or an O accumulator
+//              turns non-finite.  Every wave tests its 72 accumulators once, after the last PV, and one lane writes
+//              flags[(head * n_qblocks + query block) * 8 + wave] = 0 / 1 — every wave on every launch (no memset, no atomics).
+//   K3_REPAIR  K3_EXACT behind one test: a workgroup whose eight flags are all zero returns at once; any other recomputes its
+//              256 rows on the exact path and overwrites O (and lse) for them.
+constexpr int K3_EXACT = 0, K3_FIXED = 1, K3_REPAIR = 2;
+template <int NQ, bool SPARSE, int MODE = K3_EXACT>
 __global__ __launch_bounds__(At3<NQ>::THREADS, (NQ == 2 ? 2 : 1)) void flash_attn_fwd_kernel3(const AttnArgs p) {
     constexpr int NP = At3<NQ>::PIECES, NW = At3<NQ>::WAVES, RW = At3<NQ>::ROWS, NS = At3<NQ>::SLOTS;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -603,6 +617,10 @@ __global__ __launch_bounds__(At3<NQ>::THREADS, (NQ == 2 ? 2 : 1)) void flash_att
     int head, qb0;   // XCD-aware: the 32 CUs of an XCD walk the query blocks of ONE head together, K / V of that head come from the XCD's L2
     gf_xcd_head_block(blockIdx.x, p.heads, p.n_qblocks, head, qb0);
     const int q0 = qb0 * QB + wave * RW;
+    if constexpr (MODE == K3_REPAIR) {     // (workgroup-uniform: every wave reads the same eight words, before any barrier)
+        const int f = p.flags[((long)head * p.n_qblocks + qb0) * NW + (lane & (NW - 1))];
+        if (!__any(f != 0)) return;
+    }
 
     int vt_last = 0;     // sparse: the last V^T tile that exists (set with the list below)
     bf16x8 qf[NQ][4];   // [qb][ks]: Q[q0 + 16 qb + r][32 ks + 8 g .. +8)
@@ -790,6 +808,7 @@ __global__ __launch_bounds__(At3<NQ>::THREADS, (NQ == 2 ? 2 : 1)) void flash_att
             for (int qb = 0; qb < NQ; ++qb) mfma_pv(oacc[NDB - 1][qb], ones, pf(kk, qb));
     };
     auto apply_pending = [&]() __attribute__((always_inline)) {
+        if constexpr (MODE == K3_FIXED) return;      // (nothing is ever pending: the maximum moves once, before the first PV)
         if (pend) {
     #pragma unroll
             for (int db = 0; db < NDB; ++db)
@@ -847,16 +866,18 @@ __global__ __launch_bounds__(At3<NQ>::THREADS, (NQ == 2 ? 2 : 1)) void flash_att
     auto softmax_plain = [&](auto par_c, int t, int pos) __attribute__((always_inline)) {
         constexpr int PAR = decltype(par_c)::value;
         mask_ragged(par_c, t);
-        float mx[NQ];
+        if (MODE != K3_FIXED || pos == 0) {      // fixed-max: position 0 alone sets the maximum
+            float mx[NQ];
 #pragma unroll
-        for (int qb = 0; qb < NQ; ++qb) {
-            mx[qb] = sc[PAR][0][qb][0];
+            for (int qb = 0; qb < NQ; ++qb) {
+                mx[qb] = sc[PAR][0][qb][0];
 #pragma unroll
-            for (int kb = 0; kb < 4; ++kb)
+                for (int kb = 0; kb < 4; ++kb)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) mx[qb] = fmaxf(mx[qb], sc[PAR][kb][qb][j]);
+                    for (int j = 0; j < 4; ++j) mx[qb] = fmaxf(mx[qb], sc[PAR][kb][qb][j]);
+            }
+            new_max(par_c, mx, pos == 0);
         }
-        new_max(par_c, mx, pos == 0);
 #pragma unroll
         for (int qb = 0; qb < NQ; ++qb) {
 #pragma unroll
@@ -928,7 +949,7 @@ __global__ __launch_bounds__(At3<NQ>::THREADS, (NQ == 2 ? 2 : 1)) void flash_att
             mfma_op(s_c, par_c);
             if constexpr (S % NQ == 0) frag_load(std::integral_constant<int, S / NQ + RING - 1>{}, par_c);
             // partial maxima: slot S takes key block S / NQ of query block S % NQ (4 scores: two v_max3)
-            {
+            if constexpr (MODE != K3_FIXED) {
                 constexpr int kb = S / NQ, qb = S % NQ;
                 const f32x4& v = sc[PAR][kb][qb];
                 mx[qb] = fmaxf(fmaxf(mx[qb], v[0]), v[1]);
@@ -936,7 +957,7 @@ __global__ __launch_bounds__(At3<NQ>::THREADS, (NQ == 2 ? 2 : 1)) void flash_att
             }
             __builtin_amdgcn_sched_barrier(0);
         });
-        new_max(par_c, mx, false);
+        if constexpr (MODE != K3_FIXED) new_max(par_c, mx, false);
         float pe[2];
         gf_static_for<4 * NQ, NS>([&](auto s_c) {
             constexpr int S = decltype(s_c)::value;
@@ -1033,6 +1054,18 @@ __global__ __launch_bounds__(At3<NQ>::THREADS, (NQ == 2 ? 2 : 1)) void flash_att
     else
         pv_plain(C0{});
 
+    // ---- fixed-max: did anything overflow?  (the ninth d-block holds the row sums)
+    if constexpr (MODE == K3_FIXED) {
+        bool bad = false;
+#pragma unroll
+        for (int db = 0; db < NDB; ++db)
+#pragma unroll
+            for (int qb = 0; qb < NQ; ++qb)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) bad |= __builtin_amdgcn_classf(oacc[db][qb][e], 0x207);   // NaN, -inf, +inf
+        const int any_bad = __any(bad) ? 1 : 0;
+        if (lane == 0) p.flags[((long)head * p.n_qblocks + qb0) * NW + wave] = any_bad;
+    }
     // ---- epilogue
     {
         float inv[NQ];
@@ -1241,7 +1274,13 @@ extern "C" GF_API int gf_transpose_v32(const void* v, int64_t v_stride, void* vt
 }
 
 // gf_flash_attn_fwd_vt32 (row_ptr NULL: the dense instantiation) and gf_flash_attn_fwd_vt32_sparse: one set of checks, one launch
-static int flash_attn_vt32_impl(const char* fn, const void* q, const void* k, const void* vt, void* o, float* lse, const int32_t* row_ptr,
+// (K3_EXACT); their _fm forms (flags non-NULL): K3_FIXED, then K3_REPAIR behind it on the same stream.
+template <bool SPARSE_K, int MODE>
+static int launch_k3(const char* fn, dim3 grid, dim3 block, hipStream_t stream, const AttnArgs& a) {
+    return gf_launch_lds<flash_attn_fwd_kernel3<K3_NQ, SPARSE_K, MODE>>(fn, GF_ATTR_MSG_PLAIN, fn, grid, block, AT3_LDS, stream, a);
+}
+
+static int flash_attn_vt32_impl(const char* fn, int32_t* flags, const void* q, const void* k, const void* vt, void* o, float* lse, const int32_t* row_ptr,
                                 const int32_t* tile_idx, const int32_t* head_map, int64_t n_maps, int64_t q_len, int64_t kv_len,
                                 int64_t kv_pad, int64_t heads, int64_t head_dim, int64_t q_stride, int64_t k_stride, int64_t o_stride,
                                 float scale, void* stream) {
@@ -1287,16 +1326,35 @@ static int flash_attn_vt32_impl(const char* fn, const void* q, const void* k, co
     a.tile_idx = tile_idx;
     a.head_map = head_map;
     a.n_maps = (int)n_maps;
+    a.flags = flags;
     const dim3 grid((unsigned)(a.n_qblocks * a.heads)), block(At3<K3_NQ>::THREADS);
-    return sparse ? gf_launch_lds<flash_attn_fwd_kernel3<K3_NQ, true>>(fn, GF_ATTR_MSG_PLAIN, fn, grid, block, AT3_LDS, (hipStream_t)stream, a)
-                  : gf_launch_lds<flash_attn_fwd_kernel3<K3_NQ, false>>(fn, GF_ATTR_MSG_PLAIN, fn, grid, block, AT3_LDS, (hipStream_t)stream, a);
+    hipStream_t st = (hipStream_t)stream;
+    if (!flags) return sparse ? launch_k3<true, K3_EXACT>(fn, grid, block, st, a) : launch_k3<false, K3_EXACT>(fn, grid, block, st, a);
+    if (!gf_options().attn_fixed_max.load(std::memory_order_relaxed)) {
+        // option off: the one exact launch of the plain entry points; the flags say "nothing repaired"
+        if (hipMemsetAsync(flags, 0, sizeof(int32_t) * (size_t)(n_qblocks * heads * At3<K3_NQ>::WAVES), st) != hipSuccess) {
+            gf_set_error("%s: hipMemsetAsync(flags) failed", fn);
+            return GF_ERR_LAUNCH;
+        }
+        return sparse ? launch_k3<true, K3_EXACT>(fn, grid, block, st, a) : launch_k3<false, K3_EXACT>(fn, grid, block, st, a);
+    }
+    if (const int rc = sparse ? launch_k3<true, K3_FIXED>(fn, grid, block, st, a) : launch_k3<false, K3_FIXED>(fn, grid, block, st, a)) return rc;
+    return sparse ? launch_k3<true, K3_REPAIR>(fn, grid, block, st, a) : launch_k3<false, K3_REPAIR>(fn, grid, block, st, a);
 }
 
 extern "C" GF_API int gf_flash_attn_fwd_vt32(const void* q, const void* k, const void* vt, void* o, float* lse, int64_t q_len,
                                              int64_t kv_len, int64_t kv_pad, int64_t heads, int64_t head_dim, int64_t q_stride,
                                              int64_t k_stride, int64_t o_stride, float scale, void* stream) {
-    return flash_attn_vt32_impl("gf_flash_attn_fwd_vt32", q, k, vt, o, lse, nullptr, nullptr, nullptr, 0, q_len, kv_len, kv_pad, heads,
+    return flash_attn_vt32_impl("gf_flash_attn_fwd_vt32", nullptr, q, k, vt, o, lse, nullptr, nullptr, nullptr, 0, q_len, kv_len, kv_pad, heads,
                                 head_dim, q_stride, k_stride, o_stride, scale, stream);
+}
+
+extern "C" GF_API int gf_flash_attn_fwd_vt32_fm(const void* q, const void* k, const void* vt, void* o, float* lse, int32_t* flags,
+                                                int64_t q_len, int64_t kv_len, int64_t kv_pad, int64_t heads, int64_t head_dim,
+                                                int64_t q_stride, int64_t k_stride, int64_t o_stride, float scale, void* stream) {
+    GF_CHECK_ARG(flags && ((uintptr_t)flags & 3u) == 0, "gf_flash_attn_fwd_vt32_fm: null or misaligned flags workspace");
+    return flash_attn_vt32_impl("gf_flash_attn_fwd_vt32_fm", flags, q, k, vt, o, lse, nullptr, nullptr, nullptr, 0, q_len, kv_len, kv_pad,
+                                heads, head_dim, q_stride, k_stride, o_stride, scale, stream);
 }
 
 extern "C" GF_API int gf_flash_attn_fwd_vt32_sparse(const void* q, const void* k, const void* vt, void* o, float* lse,
@@ -1305,6 +1363,17 @@ extern "C" GF_API int gf_flash_attn_fwd_vt32_sparse(const void* q, const void* k
                                                     int64_t head_dim, int64_t q_stride, int64_t k_stride, int64_t o_stride, float scale,
                                                     void* stream) {
     GF_CHECK_ARG(row_ptr && tile_idx, "gf_flash_attn_fwd_vt32_sparse: null map pointer");
-    return flash_attn_vt32_impl("gf_flash_attn_fwd_vt32_sparse", q, k, vt, o, lse, row_ptr, tile_idx, head_map, n_maps, q_len, kv_len,
+    return flash_attn_vt32_impl("gf_flash_attn_fwd_vt32_sparse", nullptr, q, k, vt, o, lse, row_ptr, tile_idx, head_map, n_maps, q_len, kv_len,
                                 kv_pad, heads, head_dim, q_stride, k_stride, o_stride, scale, stream);
+}
+
+extern "C" GF_API int gf_flash_attn_fwd_vt32_sparse_fm(const void* q, const void* k, const void* vt, void* o, float* lse, int32_t* flags,
+                                                       const int32_t* row_ptr, const int32_t* tile_idx, const int32_t* head_map,
+                                                       int64_t n_maps, int64_t q_len, int64_t kv_len, int64_t kv_pad, int64_t heads,
+                                                       int64_t head_dim, int64_t q_stride, int64_t k_stride, int64_t o_stride,
+                                                       float scale, void* stream) {
+    GF_CHECK_ARG(row_ptr && tile_idx, "gf_flash_attn_fwd_vt32_sparse_fm: null map pointer");
+    GF_CHECK_ARG(flags && ((uintptr_t)flags & 3u) == 0, "gf_flash_attn_fwd_vt32_sparse_fm: null or misaligned flags workspace");
+    return flash_attn_vt32_impl("gf_flash_attn_fwd_vt32_sparse_fm", flags, q, k, vt, o, lse, row_ptr, tile_idx, head_map, n_maps, q_len,
+                                kv_len, kv_pad, heads, head_dim, q_stride, k_stride, o_stride, scale, stream);
 }

@@ -111,6 +111,7 @@ struct GfOptions {
     std::atomic<int> conv_gather{0};    // "conv_gather": 1 = the general (pointer-free) gather
     std::atomic<int> vae_rms3{1};       // "vae_rms3": 0 = RMS_norm+SiLU at C = 96 / 192 / 384 on the power-of-two kernel
     std::atomic<int> conv_direct{1};    // "conv_direct": 0 = the 96-channel 3x3x3 / 192-channel upsample convolutions on the implicit GEMM
+    std::atomic<int> attn_fixed_max{1}; // "attn_fixed_max": 0 = gf_flash_attn_fwd_vt32_fm / _sparse_fm make the plain entry points' one exact launch
 };
 // gf_conv_direct.hip: direct convolution of the 96-channel level; GF_ERR_UNSUPPORTED = shape not covered (caller falls back)
 int gf_conv3d_direct_c96(const void* src_walk, const void* Wm, int64_t ldw, const void* bias, void* out, int64_t T_out, int64_t H,

@@ -281,7 +281,8 @@ VT_MIN_KV = 2048   # key sequences at least this long go through the pre-transpo
 # Dispatch overrides.  Every kernel ships, each for the shapes its launcher sends it; the parity tests cross-check two kernels on
 # the SAME operands, which needs a way to route a shape to the kernel that would not get it by default.  Nothing here (and nothing
 # in the library) reads an environment variable: the defaults are the shipped dispatch and only `options(...)` changes them.
-#   library side (gf_set_option): prefer_8wave, a4_stagger, a4_group_m, conv_nb, conv_gather, conv_direct, vae_rms3
+#   library side (gf_set_option): prefer_8wave, a4_stagger, a4_group_m, conv_nb, conv_gather, conv_direct, vae_rms3,
+#                attn_fixed_max (0: kernel 3 with the running maximum in ONE launch, instead of the fixed-maximum launch + repair)
 #   this module: attn_k3 (False: long key sequences on kernel 2), vt_from_gemm (False: V^T by gf_transpose_v32, not by the V projection),
 #                conv_padded (False: the VAE's 192 / 384-channel 3x3x3 convolutions on gf_conv3d_bf16 instead of the padded-layout kernel),
 #                fold_pad_keys (False: cross-attention over all 512 context keys instead of the prompt + ONE key of multiplicity, dit.py),
@@ -289,7 +290,8 @@ VT_MIN_KV = 2048   # key sequences at least this long go through the pre-transpo
 #                vae_attn_offset (False: the VAE attention's softmax on the bf16-rounded RAW scores — one GEMM instead of two, coarser),
 #                fold_cross_o (False: the cross-attention's output projection as attention + D->D GEMM instead of probabilities x the
 #                              folded value table, dit.CrossAttention.fold_ok)
-_LIB_DEFAULTS = {"prefer_8wave": 0, "a4_stagger": 2, "a4_group_m": 0, "conv_nb": 0, "conv_gather": 0, "conv_direct": 1, "vae_rms3": 1}
+_LIB_DEFAULTS = {"prefer_8wave": 0, "a4_stagger": 2, "a4_group_m": 0, "conv_nb": 0, "conv_gather": 0, "conv_direct": 1, "vae_rms3": 1,
+                 "attn_fixed_max": 1}
 _OPT = {"attn_k3": True, "vt_from_gemm": True, "conv_padded": True, "fold_pad_keys": True, "attn_q_prescale": True, "vae_attn_offset": True,
         "fold_cross_o": True}
 
@@ -389,20 +391,36 @@ def linear_vt32_fp8(x8, x_scale, w8, bias):
     return _linear_vt32(x8, w8, x_scale, bias)
 
 
+# The flags of the last kernel-3 call on the fixed-maximum path: int32 [heads, query blocks of 256 rows, 8 waves], nonzero where a
+# wave's accumulators overflowed and its block was recomputed with the running maximum (tests and tools count repairs with it; a
+# fresh tensor per call, so it stays valid).  None after a call that took the exact path (options(attn_fixed_max=0)) or kernel 2.
+last_attn_flags = None
+
+
 def _vt_attn(lib, q, k, v, vt, out, lse, sq, skv, num_heads, head_dim, scale, k3, block_map=None):
     """The attention over a pre-transposed V, shared by flash_attn, flash_attn_lse and flash_attn_sparse: kernel 3 (16x16x32 MFMAs),
     or (k3 False: options(attn_k3=False) for the cross-check tests, a finished q) kernel 2 (32x32x16).  vt None: V^T is made here
-    from v.  block_map (a BlockMap, kernel 3 only): gf_flash_attn_fwd_vt32_sparse, which takes the map after lse."""
+    from v.  block_map (a BlockMap, kernel 3 only): gf_flash_attn_fwd_vt32_sparse, which takes the map after lse.  Kernel 3 under
+    the library option attn_fixed_max (default on): the _fm entry points — the fixed-maximum launch and its repair launch — with
+    a flags workspace of this call's own, which `last_attn_flags` keeps."""
+    global last_attn_flags
     tr, fa = (lib.gf_transpose_v32, lib.gf_flash_attn_fwd_vt32) if k3 else (lib.gf_transpose_v, lib.gf_flash_attn_fwd_vt)
-    tiles = ()
+    tiles, flags = (), ()
+    last_attn_flags = None
+    fixed = k3 and lib_option("attn_fixed_max") != 0
+    if fixed:
+        fa = lib.gf_flash_attn_fwd_vt32_fm
+        last_attn_flags = torch.empty((num_heads, -(-sq // 256), 8), dtype=torch.int32, device=q.device)
+        flags = (_ptr(last_attn_flags),)
     if block_map is not None:
-        fa = lib.gf_flash_attn_fwd_vt32_sparse
+        fa = lib.gf_flash_attn_fwd_vt32_sparse_fm if fixed else lib.gf_flash_attn_fwd_vt32_sparse
         tiles = (_ptr(block_map.row_ptr), _ptr(block_map.tile_idx), _ptr(block_map.head_map), block_map.n_maps)
     if vt is None:
         vt = _vt_workspace(num_heads * 128 * kv_pad(skv), q.device)
         _lib.check(tr(_ptr(v), v.stride(0), _ptr(vt), skv, kv_pad(skv), num_heads, _stream(q)), "gf_transpose_v")
-    _lib.check(fa(_ptr(q), _ptr(k), _ptr(vt), _ptr(out), _ptr(lse), *tiles, sq, skv, kv_pad(skv), num_heads, head_dim,
-                  q.stride(0), k.stride(0), out.stride(0), float(scale), _stream(q)), fa.__name__ if tiles else "gf_flash_attn_fwd_vt")
+    _lib.check(fa(_ptr(q), _ptr(k), _ptr(vt), _ptr(out), _ptr(lse), *flags, *tiles, sq, skv, kv_pad(skv), num_heads, head_dim,
+                  q.stride(0), k.stride(0), out.stride(0), float(scale), _stream(q)),
+               fa.__name__ if tiles or flags else "gf_flash_attn_fwd_vt")
 
 
 def flash_attn(q, k, v, num_heads, out=None, scale=None, vt=None, last_key_mult=1, finished_q=False):

@@ -55,7 +55,8 @@ GF_API int gf_abi_version(void);          /* GF_ABI_VERSION of the build */
 /* Dispatch overrides.  Every kernel in the library ships, each for the shapes its launcher sends it; the parity tests cross-check
  * two kernels on the same operands, which needs a way to route a shape to the one that would not get it by default.  Names:
  * "prefer_8wave" (0/1), "a4_stagger" (>= 0), "a4_group_m" (0 = by K), "conv_nb" (0 = by Cout, 1, 2), "conv_gather" (0/1),
- * "conv_direct" (0/1), "vae_rms3" (0/1).  Values are clamped to their range; an unknown name returns GF_ERR_INVALID_ARG.
+ * "conv_direct" (0/1), "vae_rms3" (0/1), "attn_fixed_max" (0/1, default 1; 0: gf_flash_attn_fwd_vt32_fm / _sparse_fm make the one exact
+ * launch of the plain entry points — the A/B switch and the escape hatch of the fixed-maximum softmax).  Values are clamped to their range; an unknown name returns GF_ERR_INVALID_ARG.
  * The library reads NO environment variable: only these calls change the dispatch.  Process-wide, relaxed atomics. */
 GF_API int gf_set_option(const char* name, int value);
 GF_API int gf_get_option(const char* name, int* value);   /* the value in force (after clamping); a caller that overrides one reads it first to restore it */
@@ -189,6 +190,25 @@ GF_API int gf_flash_attn_fwd_vt32_sparse(const void* q, const void* k, const voi
                                          const int32_t* row_ptr, const int32_t* tile_idx, const int32_t* head_map, int64_t n_maps,
                                          int64_t q_len, int64_t kv_len, int64_t kv_pad, int64_t heads, int64_t head_dim,
                                          int64_t q_stride, int64_t k_stride, int64_t o_stride, float scale, void* stream);
+
+/* gf_flash_attn_fwd_vt32_fm / gf_flash_attn_fwd_vt32_sparse_fm — the two entry points above with the softmax maximum FIXED at the
+ * first visited tile's row maximum m0 (dense: tile 0; sparse: the first list entry) instead of a running maximum: two launches on
+ * `stream`.  The first computes p = bf16(exp2(s - m0)) for every later tile with no maximum, no rescale decision and no rescale of
+ * O — fp32 and bf16 carry the full exponent range, and the row sum holds the exact term 1, so the result has the exact path's
+ * accuracy unless a later score lies ~100 - 128 log2 units above m0 and a row sum or an O accumulator overflows.  Each wave tests
+ * its accumulators for non-finite values and writes flags[(head * n_qblocks + b) * 8 + wave] = 0 / 1 (n_qblocks = ceil(q_len /
+ * 256); every word is written on every call: no memset needed).  The second launch returns at once in every workgroup whose eight
+ * flags are zero and recomputes the others' 256 rows with the running maximum (bit for bit what the plain entry point writes for
+ * them), overwriting o and lse.  After the call flags tells which blocks were repaired.
+ *   flags int32 [heads * n_qblocks * 8], caller-owned, 4-byte aligned, one per stream in flight.
+ * Option "attn_fixed_max" = 0: one exact launch, flags zeroed. */
+GF_API int gf_flash_attn_fwd_vt32_fm(const void* q, const void* k, const void* vt, void* o, float* lse, int32_t* flags,
+                                     int64_t q_len, int64_t kv_len, int64_t kv_pad, int64_t heads, int64_t head_dim,
+                                     int64_t q_stride, int64_t k_stride, int64_t o_stride, float scale, void* stream);
+GF_API int gf_flash_attn_fwd_vt32_sparse_fm(const void* q, const void* k, const void* vt, void* o, float* lse, int32_t* flags,
+                                            const int32_t* row_ptr, const int32_t* tile_idx, const int32_t* head_map, int64_t n_maps,
+                                            int64_t q_len, int64_t kv_len, int64_t kv_pad, int64_t heads, int64_t head_dim,
+                                            int64_t q_stride, int64_t k_stride, int64_t o_stride, float scale, void* stream);
 
 /* gf_linear_vt32 — the V projection of SelfAttention.forward (`v = self.v(x)`, DIT:131-146) written DIRECTLY in the layout
  * gf_flash_attn_fwd_vt32 reads: vt[n * kv_pad + pos(s)] = bf16(sum_k x[s,k] * w[n,k] + bias[n]) for n < N, s < kv_len, positions
