@@ -218,11 +218,12 @@ def enable_sparse_attention(module: nn.Module, pattern, dense_blocks: int = 0):
     """Block-sparse self-attention (sparse_attention.py; the reference has no counterpart): every SelfAttention inside the DiT /
     ControlNet blocks of `module` (a WanModel, a ControlNet, a block or a whole pipeline) runs ops.flash_attn_sparse on the map
     `pattern(grid)` of the token grid it is called on — a sparse_attention.FrameWindow, or any callable grid -> ops.BlockMap (the
-    hook for per-head maps).  `dense_blocks` = n keeps the first n blocks of every stack (`.blocks`) on the dense kernel.
+    hook for per-head maps) — or, for a pattern with `from_qk(q, k, num_heads, grid, scale)` (sparse_attention.MassCover), on the
+    map built on the device from that attention's own finished q and k.  `dense_blocks` = n keeps the first n blocks of every stack (`.blocks`) on the dense kernel.
     pattern=None restores the dense path bit for bit.  Inference on one GPU only: a switched block refuses training (`keep`),
     sequence parallelism, enable_sage_attention, a caller's own `freqs` (no grid) and key counts below ops.VT_MIN_KV by name instead
     of falling back.  pipe.sparse_dense_steps = n runs the first n sampling steps densely (model_fn_wan_video(sparse_dense=True))."""
-    if pattern is not None and not callable(pattern):
+    if pattern is not None and not callable(pattern) and not hasattr(pattern, "from_qk"):
         raise GoalForceError(f"enable_sparse_attention: expected a callable grid -> ops.BlockMap (or None), got {type(pattern).__name__}")
     if int(dense_blocks) != dense_blocks or dense_blocks < 0:
         raise GoalForceError(f"enable_sparse_attention: expected dense_blocks >= 0, got {dense_blocks!r}")
@@ -344,13 +345,22 @@ class SelfAttention(nn.Module):
             if x2.shape[0] < ops.VT_MIN_KV:
                 raise GoalForceError(f"sparse attention: expected at least {ops.VT_MIN_KV} tokens (ops.VT_MIN_KV, where the self-attention "
                                      f"runs on kernel 3), got {x2.shape[0]}")
-            block_map = pattern(grid)
-            if not isinstance(block_map, ops.BlockMap):
-                raise GoalForceError(f"sparse attention: expected the pattern to return an ops.BlockMap, got {type(block_map).__name__}")
-            block_map = block_map.to(rope.cos.device)
+            if hasattr(pattern, "from_qk"):
+                # a data-dependent pattern (sparse_attention.MassCover): the map is built from the finished q and k — after norm +
+                # RoPE and the pre-scaling — with the scale the attention itself gets, on the same stream
+                def attn(q, k, v, num_heads, vt=None, scale=None):
+                    block_map = pattern.from_qk(q, k, num_heads, grid, scale)
+                    if not isinstance(block_map, ops.BlockMap):
+                        raise GoalForceError(f"sparse attention: expected the pattern to return an ops.BlockMap, got {type(block_map).__name__}")
+                    return ops.flash_attn_sparse(q, k, v, num_heads, block_map, vt=vt, scale=scale)
+            else:
+                block_map = pattern(grid)
+                if not isinstance(block_map, ops.BlockMap):
+                    raise GoalForceError(f"sparse attention: expected the pattern to return an ops.BlockMap, got {type(block_map).__name__}")
+                block_map = block_map.to(rope.cos.device)
 
-            def attn(q, k, v, num_heads, vt=None, scale=None):
-                return ops.flash_attn_sparse(q, k, v, num_heads, block_map, vt=vt, scale=scale)
+                def attn(q, k, v, num_heads, vt=None, scale=None):
+                    return ops.flash_attn_sparse(q, k, v, num_heads, block_map, vt=vt, scale=scale)
         xin = (x2 if isinstance(x2, QuantizedInput) else QuantizedInput(x2)) if fp8 else x2
         # Q leaves its RMSNorm + RoPE kernel already multiplied by c = softmax scale x log2(e) (the rotation table carries the factor:
         # RopeTable.scaled), and the attention is called with scale = ln 2, i.e. c = 1 inside — its `Q <- bf16(Q c)` is then exact.

@@ -15,7 +15,7 @@ from ._lib import (EPI_BIAS, EPI_BIAS_GATE_RESID, EPI_BIAS_GELU_TANH, EPI_BIAS_M
                    GoalForceError)
 
 __all__ = [
-    "modulation", "layernorm_modulate", "rmsnorm_rope", "gate_residual", "gemm", "flash_attn", "flash_attn_sparse", "BlockMap", "patchify_im2col", "unpatchify",
+    "modulation", "layernorm_modulate", "rmsnorm_rope", "gate_residual", "gemm", "flash_attn", "flash_attn_sparse", "BlockMap", "block_means", "block_map_scores", "block_map_select", "block_map_from_qk", "patchify_im2col", "unpatchify",
     "cfg_euler_step", "act", "add", "sub", "rel_l1", "force_map",
     "EPI_BIAS", "EPI_BIAS_GELU_TANH", "EPI_BIAS_GATE_RESID", "EPI_BIAS_RESID", "EPI_BIAS_SILU", "EPI_BIAS_MUL",
 ]
@@ -480,7 +480,8 @@ class BlockMap:
     n_tiles] (a 2-D array is one map), uploaded once (`device`; None keeps it on the host, `to(device)` uploads a copy).
     `q_len` / `kv_len`: the (lowest, highest) sequence lengths the map fits; `density`: selected / all (query block, tile) pairs,
     averaged over the heads when there is a head_map.  The kernel clamps the indices but cannot validate them — this class is
-    where a map is checked: every row selects at least 2 tiles (the validated two-tile pipeline)."""
+    where a map is checked: every row selects at least 2 tiles (the validated two-tile pipeline).  `from_device` is the one other
+    constructor: a map the mass-cover kernels wrote on the device, which the host never reads unless asked."""
 
     def __init__(self, mask, head_map=None, device=None):
         mask = torch.as_tensor(mask)
@@ -513,6 +514,66 @@ class BlockMap:
         self.kv_len = ((self.n_tiles - 1) * SPARSE_KB + 1, self.n_tiles * SPARSE_KB)
         if device is not None:
             self._upload(torch.device(device))
+
+    @classmethod
+    def from_device(cls, row_ptr, tile_idx, head_map, n_maps, n_qblocks, n_tiles):
+        """A map the host never saw (ops.block_map_from_qk / block_map_select wrote it on the device): the CSR tensors are taken as
+        they are, on their device, and nothing is read back here — the kernels that write such maps guarantee the contract
+        (>= 2 ascending indices < n_tiles per row).  Shapes and dtypes are checked; `counts()` / `mask()` read back on demand, and
+        `density` is computed from `counts()` at its first use."""
+        try:
+            n_maps, n_qblocks, n_tiles = int(n_maps), int(n_qblocks), int(n_tiles)
+        except (TypeError, ValueError):
+            raise GoalForceError(f"BlockMap.from_device: expected integer n_maps / n_qblocks / n_tiles, got {n_maps!r} / {n_qblocks!r} / {n_tiles!r}") from None
+        if n_maps < 1 or n_qblocks < 1 or n_tiles < 2:
+            raise GoalForceError(f"BlockMap.from_device: expected n_maps >= 1, n_qblocks >= 1 and n_tiles >= 2, got {n_maps} / {n_qblocks} / {n_tiles}")
+        for name, t in (("row_ptr", row_ptr), ("tile_idx", tile_idx)) + ((("head_map", head_map),) if head_map is not None else ()):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous():
+                raise GoalForceError(f"BlockMap.from_device.{name}: expected a contiguous 1-D int32 tensor")
+            if t.device != row_ptr.device:
+                raise GoalForceError(f"BlockMap.from_device.{name}: expected every tensor on {row_ptr.device}, got {t.device}")
+        if row_ptr.numel() != n_maps * n_qblocks + 1:
+            raise GoalForceError(f"BlockMap.from_device.row_ptr: expected [{n_maps * n_qblocks + 1}] (n_maps * n_qblocks + 1), got [{row_ptr.numel()}]")
+        if tile_idx.numel() < 2 * n_maps * n_qblocks:
+            raise GoalForceError(f"BlockMap.from_device.tile_idx: expected room for at least 2 tiles per row ({2 * n_maps * n_qblocks}), "
+                                 f"got [{tile_idx.numel()}]")
+        self = object.__new__(cls)
+        self.n_maps, self.n_qblocks, self.n_tiles = n_maps, n_qblocks, n_tiles
+        self.row_ptr, self.tile_idx, self.head_map = row_ptr, tile_idx, head_map
+        self.q_len = ((n_qblocks - 1) * SPARSE_QB + 1, n_qblocks * SPARSE_QB)
+        self.kv_len = ((n_tiles - 1) * SPARSE_KB + 1, n_tiles * SPARSE_KB)
+        return self
+
+    @property
+    def density(self):
+        """Selected / all (query block, tile) pairs, averaged over the heads when there is a head_map.  A host-built map knows it
+        from its mask; a map born on the device (from_device) computes it at the first use, with one read-back of row_ptr."""
+        d = self.__dict__.get("_density")
+        if d is None:
+            per_map = self.counts().sum(1).double() / (self.n_qblocks * self.n_tiles)
+            d = self._density = float(per_map.mean() if self.head_map is None else per_map[self.head_map.cpu().long()].mean())
+        return d
+
+    @density.setter
+    def density(self, value):
+        self._density = float(value)
+
+    def forced_bits(self, device):
+        """This map (one map for all heads) as the `forced` operand of the mass-cover selection: int32 [n_qblocks, ceil(n_tiles / 32)]
+        on `device`, bit t % 32 of word t / 32 set for a selected tile.  Built once per device and kept on the object."""
+        if self.n_maps != 1:
+            raise GoalForceError(f"BlockMap.forced_bits: expected one map for all heads (the `always` map of a mass cover), got {self.n_maps}")
+        device = torch.device(device)
+        memo = self.__dict__.setdefault("_forced", {})
+        if device not in memo:
+            m = self.mask()[0]
+            nw = -(-self.n_tiles // 32)
+            padded = torch.zeros((self.n_qblocks, nw * 32), dtype=torch.int64)
+            padded[:, : self.n_tiles] = m
+            words = (padded.reshape(self.n_qblocks, nw, 32) << torch.arange(32)).sum(2)             # < 2^32, as int64
+            words = torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32)          # the same 32 bits
+            memo[device] = words.contiguous().to(device)
+        return memo[device]
 
     def _upload(self, device):
         self.row_ptr, self.tile_idx = self.row_ptr.to(device), self.tile_idx.to(device)
@@ -547,7 +608,7 @@ class BlockMap:
         """The bool array the map was built from, rebuilt from the CSR form (CPU)."""
         rows = torch.repeat_interleave(torch.arange(self.n_maps * self.n_qblocks), self.counts().reshape(-1))
         m = torch.zeros((self.n_maps * self.n_qblocks, self.n_tiles), dtype=torch.bool)
-        m[rows, self.tile_idx.cpu().long()] = True
+        m[rows, self.tile_idx[: rows.numel()].cpu().long()] = True         # (a device-born map's tile_idx is its worst-case buffer)
         return m.reshape(self.n_maps, self.n_qblocks, self.n_tiles)
 
 
@@ -584,10 +645,162 @@ def flash_attn_sparse(q, k, v, num_heads, block_map, out=None, scale=None, vt=No
         scale = 1.0 / math.sqrt(128)
     lse_t = torch.empty((sq, num_heads), dtype=torch.float32, device=q.device) if lse else None
     # PROFILE_ATTN's key count is what the launch computes: the selected share of the keys (FLOP figures derived from the list count
-    # 4 Sq Skv d per head; the dense Skv would overstate a sparse launch by 1 / density)
-    with _timed(PROFILE_ATTN, sq, max(1, round(skv * block_map.density)), num_heads):
+    # 4 Sq Skv d per head; the dense Skv would overstate a sparse launch by 1 / density).  Evaluated only when profiling is on: the
+    # density of a map born on the device (BlockMap.from_device) costs a read-back, which the unprofiled path must not pay
+    prof = PROFILE_ATTN
+    with _timed(prof, sq, max(1, round(skv * block_map.density)) if prof is not None else skv, num_heads):
         _vt_attn(_lib.load(), q, k, v, vt, out, lse_t, sq, skv, num_heads, 128, scale, True, block_map)
     return (out, lse_t) if lse else out
+
+
+# ---- mass-cover block maps built on the device from q and k (gf_block_map.hip; the recipe is stated in include/goalforce.h)
+BLOCK_MAP_MAX_TILES = 1024
+_BLOCK_MAP_WS = {}
+
+
+def _block_map_rows(t, name, num_heads):
+    """A [rows, heads*128] bf16 operand with contiguous rows (a column slice of a wider tensor is fine) -> (rows, row stride)."""
+    _mat(t, name)
+    if t.shape[1] != num_heads * 128:
+        raise GoalForceError(f"{name}: expected [rows, {num_heads}*128] (head_dim 128), got {tuple(t.shape)}")
+    if t.shape[0] < 1:
+        raise GoalForceError(f"{name}: empty sequence")
+    if t.stride(0) % 8 or t.data_ptr() % 16:
+        raise GoalForceError(f"{name}: row stride must be a multiple of 8 elements and the data 16-byte aligned")
+    return t.shape[0], t.stride(0)
+
+
+def _block_map_shape(op, sq, skv):
+    """(n_qblocks, n_tiles) of a map for sq queries and skv keys; the shapes the selection is not built for are refused by name."""
+    if skv < 2 * SPARSE_KB:
+        raise GoalForceError(f"{op}: expected at least {2 * SPARSE_KB} keys (two key tiles), got {skv}")
+    n_t = -(-skv // SPARSE_KB)
+    if n_t > BLOCK_MAP_MAX_TILES:
+        raise GoalForceError(f"{op}: expected at most {BLOCK_MAP_MAX_TILES} key tiles ({BLOCK_MAP_MAX_TILES * SPARSE_KB} keys), got {n_t} for {skv} keys")
+    return -(-sq // SPARSE_QB), n_t
+
+
+def _block_map_mass(op, mass):
+    try:
+        mass = float(mass)
+    except (TypeError, ValueError):
+        raise GoalForceError(f"{op}.mass: expected a number in (0, 1], got {mass!r}") from None
+    if not (0.0 < mass <= 1.0):
+        raise GoalForceError(f"{op}.mass: expected 0 < mass <= 1 (the share of the estimated softmax mass to keep), got {mass}")
+    return mass
+
+
+def _block_map_forced(op, always, n_qb, n_t, device):
+    if always is None:
+        return None
+    if not isinstance(always, BlockMap):
+        raise GoalForceError(f"{op}.always: expected an ops.BlockMap (or None), got {type(always).__name__}")
+    if always.n_maps != 1 or (always.n_qblocks, always.n_tiles) != (n_qb, n_t):
+        raise GoalForceError(f"{op}.always: expected one map of [{n_qb} query blocks, {n_t} tiles], got {always.n_maps} of "
+                             f"[{always.n_qblocks}, {always.n_tiles}]")
+    return always.forced_bits(device)
+
+
+def _block_map_workspace(nbytes, device):
+    """One reusable byte buffer per (device, stream), grown to the largest shape seen — as the sage backend's workspace."""
+    key = (device.index, torch.cuda.current_stream(device).cuda_stream)
+    ws = _BLOCK_MAP_WS.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = _BLOCK_MAP_WS[key] = torch.empty((nbytes,), dtype=torch.uint8, device=device)
+    return ws
+
+
+def _block_map_out(num_heads, n_qb, n_t, device):
+    """The caller-owned CSR buffers of one map: row_ptr, tile_idx at its worst-case capacity, head_map."""
+    return (torch.empty((num_heads * n_qb + 1,), dtype=torch.int32, device=device),
+            torch.empty((num_heads * n_qb * n_t,), dtype=torch.int32, device=device),
+            torch.empty((num_heads,), dtype=torch.int32, device=device))
+
+
+def block_means(x, num_heads, block):
+    """fp32 [heads, ceil(rows / block), 128]: the mean of x [rows, heads*128] bf16 over each run of `block` rows (256: query blocks,
+    64: key tiles; a ragged last run divides by its own count) — gf_block_means, a fixed summation order."""
+    rows, ldx = _block_map_rows(x, "block_means.x", num_heads)
+    if block not in (SPARSE_QB, SPARSE_KB):
+        raise GoalForceError(f"block_means.block: expected {SPARSE_QB} (query blocks) or {SPARSE_KB} (key tiles), got {block!r}")
+    mean = torch.empty((num_heads, -(-rows // block), 128), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.load().gf_block_means(_ptr(x), ldx, _ptr(mean), rows, num_heads, block, _stream(x)), "gf_block_means")
+    return mean
+
+
+def block_map_scores(q_mean, k_mean, q_len, kv_len, scale=None):
+    """fp32 [heads, n_qblocks, n_tiles] pooled scores in the log2 domain (gf_block_map_scores): scale x log2(e) x <q_mean, k_mean> +
+    log2(keys in the tile), from block_means(q, heads, 256) and block_means(k, heads, 64) of q_len queries and kv_len keys."""
+    n_qb, n_t = _block_map_shape("block_map_scores", q_len, kv_len)
+    for name, t, n in (("q_mean", q_mean, n_qb), ("k_mean", k_mean, n_t)):
+        _req(t, f"block_map_scores.{name}", torch.float32)
+        if t.dim() != 3 or t.shape[1:] != (n, 128) or not t.is_contiguous() or t.shape[0] != q_mean.shape[0]:
+            raise GoalForceError(f"block_map_scores.{name}: expected contiguous [heads, {n}, 128] for {q_len} queries / {kv_len} keys, "
+                                 f"got {tuple(t.shape)}")
+    heads = q_mean.shape[0]
+    scale = _sage_scale(scale)
+    scores = torch.empty((heads, n_qb, n_t), dtype=torch.float32, device=q_mean.device)
+    _lib.check(_lib.load().gf_block_map_scores(_ptr(q_mean), _ptr(k_mean), _ptr(scores), q_len, kv_len, heads, scale, _stream(q_mean)),
+               "gf_block_map_scores")
+    return scores
+
+
+def block_map_select(scores, mass, always=None, want_kept=False):
+    """The mass-cover selection and its CSR map (gf_block_map_select) from scores fp32 [heads, n_qblocks, n_tiles] (log2 domain): per
+    (head, query block) the smallest top set of tiles whose share of sum 2^score reaches `mass`, `always`'s tiles forced in, at
+    least 2 tiles, every tile for a row with a non-finite score or mass = 1 -> a BlockMap on the device, one map per head.
+    want_kept: (map, fp32 [heads, n_qblocks] estimated kept share)."""
+    _req(scores, "block_map_select.scores", torch.float32)
+    if scores.dim() != 3 or not scores.is_contiguous() or scores.shape[0] < 1 or scores.shape[1] < 1:
+        raise GoalForceError(f"block_map_select.scores: expected contiguous [heads, n_qblocks, n_tiles], got {tuple(scores.shape)}")
+    heads, n_qb, n_t = scores.shape
+    if not 2 <= n_t <= BLOCK_MAP_MAX_TILES:
+        raise GoalForceError(f"block_map_select.scores: expected 2 .. {BLOCK_MAP_MAX_TILES} key tiles, got {n_t}")
+    mass = _block_map_mass("block_map_select", mass)
+    forced = _block_map_forced("block_map_select", always, n_qb, n_t, scores.device)
+    lib = _lib.load()
+    ws = _block_map_workspace(int(lib.gf_block_map_select_workspace_bytes(n_qb, n_t, heads)), scores.device)
+    row_ptr, tile_idx, head_map = _block_map_out(heads, n_qb, n_t, scores.device)
+    kept = torch.empty((heads, n_qb), dtype=torch.float32, device=scores.device) if want_kept else None
+    _lib.check(lib.gf_block_map_select(_ptr(scores), _ptr(forced), _ptr(row_ptr), _ptr(tile_idx), _ptr(head_map), _ptr(kept), _ptr(ws),
+                                       n_qb, n_t, heads, mass, _stream(scores)), "gf_block_map_select")
+    bm = BlockMap.from_device(row_ptr, tile_idx, head_map, heads, n_qb, n_t)
+    return (bm, kept) if want_kept else bm
+
+
+def block_map_from_qk(q, k, num_heads, mass, always=None, scale=None, workspace=None, want_scores=False):
+    """The mass-cover map of one self-attention, built on the device from its own operands (gf_block_map_from_qk: pooled means,
+    pooled scores, selection, CSR — on the current stream, no host read): q [Sq, H*128], k [Skv, H*128] bf16 (row-strided views
+    OK), `scale` the softmax scale the attention will use (default 1/sqrt(128)), `mass` the share of the ESTIMATED softmax mass
+    every (head, query block) keeps, `always` an ops.BlockMap of one map whose tiles are kept whatever their score.  -> the
+    ops.BlockMap for flash_attn_sparse (one map per head); want_scores: (map, scores fp32 [H, n_qblocks, n_tiles], estimated kept
+    share fp32 [H, n_qblocks]).  `workspace`: a uint8 tensor of at least gf_block_map_workspace_bytes bytes (default: the one kept
+    per device and stream)."""
+    sq, ldq = _block_map_rows(q, "block_map_from_qk.q", num_heads)
+    skv, ldk = _block_map_rows(k, "block_map_from_qk.k", num_heads)
+    if k.device != q.device:
+        raise GoalForceError(f"block_map_from_qk: expected q and k on one device, got {q.device} / {k.device}")
+    n_qb, n_t = _block_map_shape("block_map_from_qk", sq, skv)
+    mass = _block_map_mass("block_map_from_qk", mass)
+    scale = _sage_scale(scale)
+    forced = _block_map_forced("block_map_from_qk", always, n_qb, n_t, q.device)
+    lib = _lib.load()
+    nbytes = int(lib.gf_block_map_workspace_bytes(sq, skv, num_heads))
+    if workspace is None:
+        workspace = _block_map_workspace(nbytes, q.device)
+    else:
+        _req(workspace, "block_map_from_qk.workspace", torch.uint8)
+        if workspace.numel() < nbytes or not workspace.is_contiguous() or workspace.data_ptr() % 256 or workspace.device != q.device:
+            raise GoalForceError(f"block_map_from_qk.workspace: expected a contiguous, 256-byte aligned uint8 buffer of at least {nbytes} "
+                                 f"bytes on {q.device}")
+    row_ptr, tile_idx, head_map = _block_map_out(num_heads, n_qb, n_t, q.device)
+    scores = torch.empty((num_heads, n_qb, n_t), dtype=torch.float32, device=q.device) if want_scores else None
+    kept = torch.empty((num_heads, n_qb), dtype=torch.float32, device=q.device) if want_scores else None
+    _lib.check(lib.gf_block_map_from_qk(_ptr(q), ldq, _ptr(k), ldk, _ptr(forced), _ptr(row_ptr), _ptr(tile_idx), _ptr(head_map),
+                                        _ptr(scores), _ptr(kept), _ptr(workspace), sq, skv, num_heads, scale, mass, _stream(q)),
+               "gf_block_map_from_qk")
+    bm = BlockMap.from_device(row_ptr, tile_idx, head_map, num_heads, n_qb, n_t)
+    return (bm, scores, kept) if want_scores else bm
 
 
 # ---- SageAttention backend (gf_sage_attention.hip; the recipe is stated in include/goalforce.h)

@@ -2,8 +2,10 @@
 
 The mechanism is ops.flash_attn_sparse: kernel 3 over a list of 64-key tiles per 256-row query block (ops.BlockMap).  A pattern
 is any callable `grid -> ops.BlockMap`, grid = the (f, h, w) token grid of the latent video; the blocks ask it for the map of the
-grid they run on.  One family ships, FrameWindow: it needs no token reordering, because the DiT's tokens are already in
-(f, h, w) order and a window of frames is then a band of tiles.
+grid they run on.  Two families ship.  FrameWindow is static: it needs no token reordering, because the DiT's tokens are already
+in (f, h, w) order and a window of frames is then a band of tiles.  MassCover is data-dependent: the blocks hand it the finished
+q and k of every self-attention (`from_qk`), and it builds, on the device, per head the smallest set of tiles whose ESTIMATED
+softmax mass reaches a requested share (ops.block_map_from_qk; the recipe is stated in include/goalforce.h).
 
 The reference has no counterpart (its flash_attention is dense on every backend), so nothing here is pinned against it, and
 what a sparse pattern does to the videos of a trained checkpoint is NOT measured in this repository: the switch
@@ -16,7 +18,7 @@ import torch
 from . import ops
 from ._lib import GoalForceError
 
-__all__ = ["FrameWindow", "frame_window_mask"]
+__all__ = ["FrameWindow", "MassCover", "frame_window_mask"]
 
 
 def _check_grid(grid):
@@ -81,3 +83,49 @@ class FrameWindow:
                 self._maps[(grid, None)] = ops.BlockMap(self.mask(grid))
             self._maps[key] = self._maps[(grid, None)].to(device) if device is not None else self._maps[(grid, None)]
         return self._maps[key]
+
+
+class MassCover:
+    """Data-dependent sparse attention: before every self-attention, q is pooled per 256-row query block and k per 64-key tile, every
+    (block, tile) pair is scored with the pooled vectors, and per head and query block the smallest top set of tiles whose estimated
+    share of the row's softmax mass reaches `mass` is kept (at least 2 tiles; ties taken together; a row with a non-finite score
+    keeps everything) — ops.block_map_from_qk, on the attention's stream, with no host round trip.  `always`: a static pattern
+    (a FrameWindow, or any callable grid -> ops.BlockMap of one map) whose tiles are kept whatever their score, or None.
+    `mass` = 1 keeps every tile: the dense kernel's bits.  Flat attention degrades towards the dense map (density ~ mass), peaky
+    attention keeps few tiles.  The mass is an ESTIMATE from pooled vectors (a Jensen lower bound of each tile's mass seen from the
+    block's mean query), not a guarantee for the block's actual rows; the true retained mass of a run is 2^(lse_sparse - lse_dense)
+    (tools/adaptive_map_bench.py measures it).  `keep_last`: the last built map stays as `.last_map` (tests, the bench).
+    The blocks call `from_qk(q, k, num_heads, grid, scale)`; there is no map without q and k, so `pattern(grid)` is refused."""
+
+    def __init__(self, mass: float, always=None, keep_last: bool = False):
+        try:
+            ok = 0.0 < float(mass) <= 1.0
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise GoalForceError(f"MassCover: expected 0 < mass <= 1, got mass={mass!r}")
+        if always is not None and not callable(always):
+            raise GoalForceError(f"MassCover: expected `always` to be a static pattern grid -> ops.BlockMap (or None), got {type(always).__name__}")
+        if hasattr(always, "from_qk"):
+            raise GoalForceError(f"MassCover: expected `always` to be a static pattern, got the data-dependent {always!r}")
+        self.mass, self.always, self.keep_last = float(mass), always, bool(keep_last)
+        self.last_map = None
+
+    def __repr__(self):
+        return f"MassCover({self.mass}, always={self.always!r})"
+
+    def __call__(self, grid, device=None):
+        raise GoalForceError(f"{self!r} has no map without q and k: the blocks call from_qk(q, k, num_heads, grid, scale)")
+
+    def from_qk(self, q, k, num_heads, grid, scale=None) -> ops.BlockMap:
+        """The map of one self-attention on its finished q and k (after norm + RoPE, pre-scaled or not: `scale` is the softmax scale
+        the attention is then called with)."""
+        always = None
+        if self.always is not None:
+            always = self.always(_check_grid(grid))
+            if not isinstance(always, ops.BlockMap):
+                raise GoalForceError(f"MassCover: expected `always` to return an ops.BlockMap, got {type(always).__name__}")
+        block_map = ops.block_map_from_qk(q, k, num_heads, self.mass, always=always, scale=scale)
+        if self.keep_last:
+            self.last_map = block_map
+        return block_map

@@ -298,6 +298,46 @@ GF_API int gf_f32_to_bf16(const float* src, void* dst, int64_t n, void* stream);
 GF_API int gf_sumsq(const void* x, int64_t n, float* acc, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Mass-cover block maps (gf_block_map.hip; the reference has no counterpart): the CSR map of gf_flash_attn_fwd_vt32_sparse built
+ * on the device from that call's own q and k, per head, with no host read.  Operands as there: q [q_len][ldq], k [kv_len][ldk]
+ * bf16, heads * 128 columns used (head_dim 128), row strides multiples of 8 elements, 16-byte aligned; n_qb = ceil(q_len / 256),
+ * n_t = ceil(kv_len / 64); kv_len >= 128 and n_t <= 1024 (else GF_ERR_INVALID_ARG, by name).  The recipe (this project's own, in the
+ * line of SpargeAttn / XAttention / MInference):
+ *   1. pooling   qm[h][b][:] = fp32 mean of the rows of query block b that exist (a ragged last block divides by its own count);
+ *                km[h][t][:] = the same over the keys of tile t.  Sum order: a lane's rows 16 apart ascending, then a fixed tree.
+ *   2. scores    s[h][b][t] = fma(c, dot, log2(n_keys(t))), dot = fma chain over d = 0 .. 127, c = fp32(double(scale) * log2(e))
+ *                (the package's pre-scaled q with scale = ln 2 gives c = 1); n_keys(t) = 64, or the ragged last tile's count.
+ *                By Jensen's inequality n_keys 2^dot-term is a LOWER bound of the tile's true unnormalised mass seen from the pooled
+ *                query — for the block's actual rows it is an ESTIMATE, not a guarantee.
+ *   3. selection per row (h, b): M = max_t s, w_t = exp2(s_t - M), W = sum_t w_t; `forced` (uint32 [n_qb][ceil(n_t / 32)], bit t % 32
+ *                of word t / 32, shared by all heads, NULL = none; bits >= n_t ignored) names tiles that are always kept, F = their
+ *                mass.  theta* = the largest value among the w_t with F + sum{w_u : u not forced, w_u >= theta*} >= mass * W; selected =
+ *                forced U {u : w_u >= theta*}; forced only when F >= mass * W.  A threshold on the value: ties are taken together.
+ *                Fewer than 2 selected: the largest unselected w is added (lowest index on ties) until there are 2.  mass >= 1
+ *                selects every tile.  A row with ANY non-finite score selects every tile — so every emitted row is valid (>= 2
+ *                ascending indices < n_t) for any input bits.  All sums are fp32 in one fixed order.
+ *   4. emit      row_ptr int32 [heads * n_qb + 1] (row_ptr[0] = 0, a scan of the counts on the device), tile_idx int32 ascending
+ *                inside a row, caller-owned with capacity heads * n_qb * n_t (the worst case), head_map int32 [heads] = 0 .. heads-1;
+ *                the sparse kernel takes them with n_maps = heads.
+ * Optional outputs (NULL to skip): scores fp32 [heads][n_qb][n_t]; kept fp32 [heads * n_qb], the ESTIMATED kept share
+ * sum_selected w / W (1 for a row that selects everything).  The true retained mass of a run is 2^(lse_sparse - lse_dense).
+ * No atomics: two calls on the same operands write the same bits; gf_block_map_from_qk writes the bits of the staged calls
+ * (gf_block_means x 2, gf_block_map_scores, gf_block_map_select), which it runs on `stream` in that order.
+ *   ws of gf_block_map_from_qk: gf_block_map_workspace_bytes bytes, 256-byte aligned (qm, km, scores, the selection's scratch);
+ *   ws of gf_block_map_select: gf_block_map_select_workspace_bytes bytes (counts and selection bitmasks).  One per stream in flight. */
+GF_API int64_t gf_block_map_workspace_bytes(int64_t q_len, int64_t kv_len, int64_t heads);     /* 0: a shape the entry refuses */
+GF_API int64_t gf_block_map_select_workspace_bytes(int64_t n_qblocks, int64_t n_tiles, int64_t heads);
+/* mean fp32 [heads][ceil(rows / block)][128]; block = 256 (query blocks) or 64 (key tiles) */
+GF_API int gf_block_means(const void* x, int64_t ldx, float* mean, int64_t rows, int64_t heads, int64_t block, void* stream);
+GF_API int gf_block_map_scores(const float* q_mean, const float* k_mean, float* scores, int64_t q_len, int64_t kv_len, int64_t heads,
+                               float scale, void* stream);
+GF_API int gf_block_map_select(const float* scores, const uint32_t* forced, int32_t* row_ptr, int32_t* tile_idx, int32_t* head_map,
+                               float* kept, void* ws, int64_t n_qblocks, int64_t n_tiles, int64_t heads, float mass, void* stream);
+GF_API int gf_block_map_from_qk(const void* q, int64_t ldq, const void* k, int64_t ldk, const uint32_t* forced, int32_t* row_ptr,
+                                int32_t* tile_idx, int32_t* head_map, float* scores, float* kept, void* ws, int64_t q_len,
+                                int64_t kv_len, int64_t heads, float scale, float mass, void* stream);
+
+/* ------------------------------------------------------------------------
  * gf_patchify_im2col — gathers the (1,2,2) patches of an NCTHW latent into a
  * token-major matrix for the patch-embedding GEMM.  Replaces the data movement
  * of WanModel.patchify (DIT:341-349) / ControlNet_PatchEmbedding.forward
