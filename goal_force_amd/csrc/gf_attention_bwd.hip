@@ -51,6 +51,8 @@ struct BwdArgs {
 //     the first MFMA's C operand, and the file is built with -fno-slp-vectorize (v_pk_mul_f32 costs more beside MFMAs than two v_mul).
 // Arithmetic per element as in the first kernels (p = exp2(fma(S, c, -lse)), dS = p (dP - delta), one rounding to bf16 per MFMA
 // operand); the summation ORDER over keys / queries differs (16x16x32 adds 32 products per step), so results differ in the last bits.
+// lse may be any finite log2-domain value (tests/test_attention_bwd_gpu.py runs -140 and +155): no padded row's exp2 reaches a product
+// unclamped.  What grows with |lse| is only fp32's own spacing in fma(S, c, -lse): a relative error of ~2^-24 |lse| ln 2 in P.
 constexpr int GR = 32;                         // queries per granule of the dK/dV kernel
 constexpr int GR_BYTES = GR * HD * 2;          // 8 KiB: one operand array of one granule
 constexpr int KV16_RING = 4;
@@ -233,8 +235,12 @@ __global__ __launch_bounds__(DQ_THREADS, 2) void attn_bwd_dq16_kernel(const Bwd1
         ptr[db] = lds + fo.tr[db];
         asm volatile("" : "+v"(ptr[db]));
     }
-    // No masking of a ragged last tile: rows past kv_len arrive as zeros, so those keys' dS (finite: p = exp2(-lse), dP = 0) meets a
-    // zero row of K in the last product.
+    // No masking of a ragged last tile: rows past kv_len arrive as zeros, so those keys' dS (p (0 - delta)) meets a zero row of K in the
+    // last product — which is exactly zero only while dS is FINITE.  A padded key's p = exp2(0 c - lse) overflows for lse < -128 (a query
+    // whose scores all lie far below zero), and inf x 0 = NaN reached every dQ element of that query whenever kv_len % 64 != 0.  Hence the
+    // clamp of p to [0, 1] in `softmax` below: a real key's p is <= 1 up to rounding (lse >= every c S), a padded key's becomes 1, and the
+    // clamp is an output modifier of the exp2 instruction, so the per-score path is as long as before.  (The dK/dV kernel needs none: its
+    // padded QUERIES carry the record lse = 0, delta = 0 -> p = 1, dS = 0; its keys past kv_len are clamped copies that are never stored.)
     // One 32-key half of a tile; the order is pinned by scheduling barriers (left alone, hipcc reads a fragment, waits for it, issues its
     // two MFMAs, and so on — the matrix pipe idles through every LDS round trip).  F = 8 fragment registers, refilled in halves as soon as
     // the MFMAs that read them have been issued; the exp2 / dS arithmetic of key block 2 h is INTERLEAVED with the MFMAs of block 2 h + 1
@@ -278,7 +284,8 @@ __global__ __launch_bounds__(DQ_THREADS, 2) void attn_bwd_dq16_kernel(const Bwd1
                 float x[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const float pr = __builtin_amdgcn_exp2f(__builtin_fmaf(sc[kbb][qb][j], c, -lse[qb]));
+                    // clamped to [0, 1] (the output modifier of v_exp_f32: no instruction of its own): a padded key's exp2(-lse)
+                    const float pr = __builtin_amdgcn_fmed3f(__builtin_amdgcn_exp2f(__builtin_fmaf(sc[kbb][qb][j], c, -lse[qb])), 0.f, 1.f);
                     x[j] = pr * dp[kbb][qb][j];
                 }
                 dsw[qb][2 * kbb] = pack2bf(x[0], x[1]);
