@@ -59,11 +59,13 @@ def add_rise(q, k, h, row, key, rise, first_keys=range(TILE)):
 WAVE_ROWS = 32
 
 
-def model(s, v, schedule, quiet=6.0):
+def model(s, v, schedule, quiet=6.0, sum_rounded_p=True, rescale_l=True):
     """Kernel 3's arithmetic for one head on the CPU: fp32 scores `s` [sq, skv] in the exp2 domain, p = bf16(exp2(s - m)), fp32 row
     sums and fp32 O over 64-key tiles.  schedule "running": when a tile's row maximum lies more than `quiet` above m for any of a
     wave's 32 rows (the lazy rescale is a per-wave decision), every row of the wave moves its m up to its tile maximum and
-    rescales O and l;  "fixed": m stays tile 0's row maximum.  Returns (O / l [sq, 128] fp32, l [sq] fp32, m [sq] fp32) — l is
+    rescales O and l;  "fixed": m stays tile 0's row maximum.  sum_rounded_p False: the row sum takes the fp32 p before its
+    rounding, as kernel 2's does;  rescale_l False: a move of the maximum rescales O alone (a fault that
+    tests/attention_fwd_refs.py injects).  Returns (O / l [sq, 128] fp32, l [sq] fp32, m [sq] fp32) — l is
     what the kernel's overflow test looks at."""
     s = s.float()
     v = v.float()
@@ -79,9 +81,10 @@ def model(s, v, schedule, quiet=6.0):
                 if not bool((d[r0:r0 + WAVE_ROWS] > quiet).any()):
                     d[r0:r0 + WAVE_ROWS] = 0.0
             alpha = torch.exp2(-d)
-            o, l, m = o * alpha[:, None], l * alpha, m + d
-        p = torch.exp2(st - m[:, None]).to(BF).float()
-        l = l + p.sum(dim=1)
+            o, l, m = o * alpha[:, None], (l * alpha if rescale_l else l), m + d
+        p32 = torch.exp2(st - m[:, None])
+        p = p32.to(BF).float()
+        l = l + (p if sum_rounded_p else p32).sum(dim=1)
         o = o + p @ v[t0:t0 + TILE]
     return o / l[:, None], l, m
 

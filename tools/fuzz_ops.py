@@ -5,7 +5,8 @@ authors thought of); this draws shapes nobody picked — row counts around the t
 lengths around the 64-key tile and the 2048-key kernel switch, strided operands (q / k / v as column slices of one fused buffer), every
 GEMM epilogue, in-place residuals — and reports every case whose error exceeds the operator's bar, or whose call fails without being a
 refusal the header documents.  Exit code 1 when anything failed.  `--only fwdrows` (not part of the default sweep) holds the forward
-row kernels against the exact chains of tests/forward_refs.py."""
+row kernels against the exact chains of tests/forward_refs.py, `--only attnfwd` (opt-in as well) the attention forward's entry points
+against the bounds of tests/attention_fwd_refs.py."""
 import argparse
 import math
 import os
@@ -359,9 +360,66 @@ def case_fwdrows(rnd, g):
     return f"rmsnorm_rope rows={rows} dim={dim} head_dim={hd} rope={cos is not None}", err_of(xg, *chain), 1.0
 
 
+def case_attnfwd(rnd, g):
+    """The attention forward through the raw C ABI against the fp64 reference and the bounds of tests/attention_fwd_refs.py (element
+    bound, row bar, lse bound; err = the worst of the three shares, bar 1): a random entry point of kernel 2 (plain, lse, V^T, last-key
+    multiplicity) or kernel 3 (exact, fixed maximum, block-sparse with a random ascending map in either mode) — kernel 3 from 128 keys,
+    far below the length from which ops.flash_attn picks it — random lengths up to 513, 1 - 4 or 8 heads, a random data class."""
+    if os.path.join(ROOT, "tests") not in sys.path:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import attention_fwd_refs as R
+    from goal_force_amd import _lib
+    lib, st = _lib.load(), torch.cuda.current_stream().cuda_stream
+    entry = rnd.choice(["fwd", "fwd_lse", "fwd_vt", "fwd_lastmult", "fwd_vt32", "fwd_vt32_fm", "fwd_vt32_sparse", "fwd_vt32_sparse_fm"])
+    k3 = "vt32" in entry
+    sq = rnd.choice([rnd.choice(R.Q_LENS), rnd.randrange(1, 514)])
+    skv = rnd.choice([rnd.choice(R.K3_KV if k3 else R.K2_KV), rnd.randrange(128 if k3 else 1, 514)])
+    heads = rnd.choice([1, 2, 3, 4, 8])
+    name = rnd.choice(["std1", "std3", "std8", "prescaled", "far_below", "far_above", "v_const", "k_zero"])
+    mult = rnd.choice([2, 3, 472]) if entry == "fwd_lastmult" else 1
+    q, k, v, scale = R.case_inputs(name, sq, skv, heads)
+    lists = sel = None
+    nt, nb = -(-skv // 64), -(-sq // 256)
+    if "sparse" in entry:
+        lists = [[sorted(rnd.sample(range(nt), rnd.randrange(1, nt + 1))) for _ in range(nb)] for _ in range(rnd.choice([1, 2]))]
+        hm = [rnd.randrange(len(lists)) for _ in range(heads)] if len(lists) > 1 or rnd.random() < 0.5 else None
+        sel = R.selection(lists, hm, heads, sq, skv)
+    ref = R.attn_ref(q, k, v, heads, scale, mult, sel)
+    qd, kd, vd = q.cuda(), k.cuda(), v.cuda()
+    o = torch.empty_like(qd)
+    lse = torch.empty((sq, heads), dtype=torch.float32, device="cuda") if entry not in ("fwd", "fwd_lastmult") else None
+    kvp, D = nt * 64, heads * 128
+    lens = (sq, skv, heads, 128, D, D, D, D, scale)
+    if entry in ("fwd", "fwd_lse", "fwd_lastmult"):
+        extra = {"fwd": (), "fwd_lse": (), "fwd_lastmult": (float(mult),)}[entry]
+        ptrs = (qd.data_ptr(), kd.data_ptr(), vd.data_ptr(), o.data_ptr()) + ((lse.data_ptr(),) if lse is not None else ())
+        rc = getattr(lib, "gf_flash_attn_" + entry)(*ptrs, *lens, *extra, st)
+    else:
+        vt = torch.empty((D * kvp,), dtype=BF, device="cuda")
+        _lib.check((lib.gf_transpose_v32 if k3 else lib.gf_transpose_v)(vd.data_ptr(), D, vt.data_ptr(), skv, kvp, heads, st), "transpose")
+        mid = ()
+        if entry.endswith("_fm"):
+            flags = torch.empty((heads * nb * 8,), dtype=torch.int32, device="cuda")
+            mid += (flags.data_ptr(),)
+        if lists is not None:
+            rp, ti = (t.cuda() for t in R.csr(lists))
+            hmd = None if hm is None else torch.tensor(hm, dtype=torch.int32).cuda()
+            mid += (rp.data_ptr(), ti.data_ptr(), None if hmd is None else hmd.data_ptr(), len(lists))
+        rc = getattr(lib, "gf_flash_attn_" + entry)(qd.data_ptr(), kd.data_ptr(), vt.data_ptr(), o.data_ptr(), lse.data_ptr(), *mid,
+                                                    sq, skv, kvp, heads, 128, D, D, D, scale, st)
+    _lib.check(rc, entry)
+    torch.cuda.synchronize()
+    kind = "k2" if not k3 else ("k3fm" if entry.endswith("_fm") else "k3")
+    n, we, wr = R.measure(o.cpu(), ref, kind)
+    err = max(we, wr / R.row_bar(kind, scale))
+    if lse is not None:
+        err = max(err, R.measure_lse(lse.cpu(), ref, kind)[1])
+    return f"attnfwd {entry} q={sq} kv={skv} heads={heads} {name} mult={mult} maps={lists}", err, 1.0
+
+
 CASES = {"gemm": case_gemm, "attn": case_attn, "rows": case_rows, "cfg": case_cfg, "attnbwd": case_attnbwd, "fp8": case_fp8,
-         "batched": case_batched, "misc": case_misc, "bwdrows": case_bwdrows, "fwdrows": case_fwdrows}
-OPT_IN = ("fwdrows",)       # run with --only alone (bwdrows is in the default sweep): the default sweep, and the suite's run of it, stays what it was
+         "batched": case_batched, "misc": case_misc, "bwdrows": case_bwdrows, "fwdrows": case_fwdrows, "attnfwd": case_attnfwd}
+OPT_IN = ("fwdrows", "attnfwd")       # run with --only alone (bwdrows is in the default sweep): the default sweep, and the suite's run of it, stays what it was
 
 
 def main():
