@@ -2,7 +2,8 @@
 // pooled means per query block / key tile, pooled scores in the log2 domain, per (head, query block) the smallest top set of tiles
 // whose estimated softmax mass reaches tau, written as the CSR map gf_flash_attn_fwd_vt32_sparse reads.  Five small kernels on the
 // caller's stream, no host read, no atomics: every sum has ONE order (a lane's own elements in index order, the wave's xor
-// butterfly, the waves in wave order), so two calls on the same operands give the same bits.
+// butterfly, the waves in wave order), so two calls on the same operands give the same bits.  The gated entries add the coherence of
+// every block (step 1b, on the pooling pass's own loads) and refuse to predict for incoherent query blocks and key tiles (step 3).
 #include "gf_common.h"
 
 namespace {
@@ -12,6 +13,7 @@ constexpr int BM_MAX_TILES = 1024;          // the selection keeps a row's tiles
 constexpr int BM_THREADS = 256;
 
 static inline int64_t align256(int64_t n) { return (n + 255) & ~(int64_t)255; }
+__device__ __forceinline__ bool bm_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
 // ---------------------------------------------------------------------------------------------------------------- 1. pooling
 // mean[h][b][c] = (sum over the rows of block b that exist of x[row][h*128 + c]) / their count.  One workgroup per (block, head):
@@ -49,6 +51,76 @@ __global__ __launch_bounds__(BM_THREADS) void block_means_kernel(const u16* __re
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------ 1b. coherence
+// block_means_kernel with one more accumulator per lane on the same loads: rho = |mean|^2 / e, e = (sum over the block's rows of
+// |x_i|^2) / their count — 1 when the rows are equal, 1 / n for orthogonal rows of one norm, 0 when they cancel.  The means are
+// summed in block_means_kernel's order and have its bits.  Order of e's sum: per lane the fma chain e = fma(x, x, e) over the row's 8
+// channels, rows ascending; the 16 channel-group lanes cg ^ 1, ^ 2, ^ 4, ^ 8; row groups g ^ 1, g ^ 2; waves 0, 1, 2, 3; / count.
+// |mean|^2 from the finished fp32 means: lane l of wave 0 forms fma(m[l + 64], m[l + 64], m[l] * m[l]), then l ^ 1, ^ 2, .. ^ 32.
+// e == 0 (every row zero: all rows are equal) gives 1; a non-finite e or quotient (non-finite input, or finite input whose squares
+// overflow fp32 — conservative) is written as NaN, which the gate's `!(rho >= min)` counts as incoherent.
+template <int BLOCK>
+__global__ __launch_bounds__(BM_THREADS) void block_means_coh_kernel(const u16* __restrict__ x, int64_t ldx, float* __restrict__ mean,
+                                                                     float* __restrict__ coh, int rows, int n_blocks) {
+    __shared__ float red[4][16][8];
+    __shared__ float ered[4];
+    __shared__ float ml[128];
+    const int b = blockIdx.x, h = blockIdx.y, tid = threadIdx.x;
+    const int cg = tid & 15, rg = tid >> 4;
+    const int r0 = b * BLOCK, n = min(BLOCK, rows - r0);
+    const u16* src = x + (int64_t)r0 * ldx + h * 128 + cg * 8;
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float e = 0.f;
+#pragma unroll 4
+    for (int i = rg; i < n; i += 16) {
+        const u16x8 v = *reinterpret_cast<const u16x8*>(src + (int64_t)i * ldx);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float f = bf2f(v[j]);
+            acc[j] += f;
+            e = __builtin_fmaf(f, f, e);
+        }
+    }
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) e += __shfl_xor(e, o);
+    e += __shfl_xor(e, 16);
+    e += __shfl_xor(e, 32);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        acc[j] += __shfl_xor(acc[j], 16);
+        acc[j] += __shfl_xor(acc[j], 32);
+    }
+    if ((tid & 63) < 16) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) red[tid >> 6][cg][j] = acc[j];
+    }
+    if ((tid & 63) == 0) ered[tid >> 6] = e;
+    __syncthreads();
+    if (tid < 128) {
+        const int g = tid >> 3, j = tid & 7;
+        const float s = ((red[0][g][j] + red[1][g][j]) + red[2][g][j]) + red[3][g][j];
+        const float m = s / (float)n;
+        mean[((int64_t)h * n_blocks + b) * 128 + tid] = m;
+        ml[tid] = m;
+    }
+    __syncthreads();
+    if (tid < 64) {
+        const float lo = ml[tid], hi = ml[tid + 64];
+        float p = __builtin_fmaf(hi, hi, lo * lo);
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) p += __shfl_xor(p, o);
+        if (tid == 0) {
+            const float en = (((ered[0] + ered[1]) + ered[2]) + ered[3]) / (float)n;
+            float rho = 1.0f;
+            if (en != 0.f) {
+                rho = p / en;
+                if (!bm_finite(en) || !bm_finite(rho)) rho = __builtin_nanf("");
+            }
+            coh[(int64_t)h * n_blocks + b] = rho;
+        }
+    }
+}
+
 // ----------------------------------------------------------------------------------------------------------------- 2. scores
 // s[h][b][t] = fma(c, dot, log2(n_keys(t))), dot = the fma chain over d = 0 .. 127 from 0.  One workgroup per (64 tiles, head): the
 // tiles' means sit in LDS (row pitch 129 floats: lane t reads bank (t + d) % 64), wave w takes the query blocks w, w + 4, ...
@@ -77,8 +149,6 @@ __global__ __launch_bounds__(BM_THREADS) void block_scores_kernel(const float* _
 }
 
 // -------------------------------------------------------------------------------------------------------------- 3. selection
-__device__ __forceinline__ bool bm_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-
 // block-wide integer sum, fp32 maximum and 64-bit maximum in the shape of gf_common.h's block_sum (256 threads)
 __device__ __forceinline__ int bm_block_isum(int v, int* red) {
 #pragma unroll
@@ -113,9 +183,15 @@ __device__ __forceinline__ unsigned long long bm_block_umax(unsigned long long v
 
 // One workgroup per row r = h * n_qb + b; thread i holds the tiles 4 i .. 4 i + 3.  Writes counts[r], the selection as a bitmask
 // bits[r][n_words] (bit t % 32 of word t / 32) and, when asked, the estimated kept share.
+// GATED (gf_block_map_select_gated; the ungated instantiation is the code it was): a row whose query block is incoherent,
+// !(q_coh[r] >= q_min), takes the path of a non-finite score; a tile with !(k_coh[h][t] >= k_min) is one more forced tile of every row
+// of head h — each thread reads the coherences of its own four tiles.  `!(>=)`: a NaN coherence fires.  A null q_coh / k_coh: no gate.
+template <bool GATED>
 __global__ __launch_bounds__(BM_THREADS) void block_select_kernel(const float* __restrict__ scores, const uint32_t* __restrict__ forced,
                                                                   int32_t* __restrict__ counts, uint32_t* __restrict__ bits,
-                                                                  float* __restrict__ kept, int n_qb, int n_t, int n_words, float mass) {
+                                                                  float* __restrict__ kept, int n_qb, int n_t, int n_words, float mass,
+                                                                  const float* __restrict__ q_coh, const float* __restrict__ k_coh,
+                                                                  float q_min, float k_min) {
     __shared__ float fred[4];
     __shared__ int ired[4];
     __shared__ unsigned long long ured[4];
@@ -135,6 +211,15 @@ __global__ __launch_bounds__(BM_THREADS) void block_select_kernel(const float* _
         forc[j] = valid[j] && ((fword >> ((tid & 7) * 4 + j)) & 1u);
         bad = bad || !bm_finite(s[j]);
         if (valid[j]) m = fmaxf(m, s[j]);
+    }
+    if constexpr (GATED) {
+        if (k_coh != nullptr) {
+            const float* kc = k_coh + (int64_t)(r / n_qb) * n_t;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (valid[j] && !(kc[tid * 4 + j] >= k_min)) forc[j] = true;
+        }
+        if (q_coh != nullptr && !(q_coh[r] >= q_min)) bad = true;      // the same value in every thread of the row
     }
     const bool full = __syncthreads_or(bad) || !(mass < 1.0f);      // a non-finite score, or tau >= 1 (a NaN tau too): every tile
     float share = 1.0f;
@@ -279,17 +364,36 @@ static int check_shape(const char* who, int64_t q_len, int64_t kv_len, int64_t h
     return GF_OK;
 }
 
-static int launch_means(const char* who, const void* x, int64_t ldx, float* mean, int64_t rows, int64_t heads, int64_t block, hipStream_t st) {
+static int check_means(const char* who, const void* x, int64_t ldx, const float* mean, int64_t rows, int64_t heads, int64_t block) {
     GF_CHECK_ARG(x && mean, "%s: null pointer", who);
     GF_CHECK_ARG(block == BM_QB || block == BM_KB, "%s: expected block 256 (query blocks) or 64 (key tiles), got %lld", who, (long long)block);
     GF_CHECK_ARG(rows >= 1 && rows < ((int64_t)1 << 31) && heads >= 1 && heads <= 65535, "%s: expected 1 <= rows < 2^31 and 1 <= heads <= 65535", who);
     GF_CHECK_ARG(ldx >= heads * 128 && ldx % 8 == 0 && gf_aligned16(x), "%s: expected a row stride >= heads*128 that is a multiple of 8 elements and 16-byte aligned data", who);
+    return GF_OK;
+}
+
+static int launch_means(const char* who, const void* x, int64_t ldx, float* mean, int64_t rows, int64_t heads, int64_t block, hipStream_t st) {
+    if (int e = check_means(who, x, ldx, mean, rows, heads, block)) return e;
     const int nb = (int)((rows + block - 1) / block);
     const dim3 grid(nb, (unsigned)heads);
     if (block == BM_QB)
         block_means_kernel<BM_QB><<<grid, BM_THREADS, 0, st>>>((const u16*)x, ldx, mean, (int)rows, nb);
     else
         block_means_kernel<BM_KB><<<grid, BM_THREADS, 0, st>>>((const u16*)x, ldx, mean, (int)rows, nb);
+    GF_CHECK_LAUNCH(who);
+    return GF_OK;
+}
+
+static int launch_means_coh(const char* who, const void* x, int64_t ldx, float* mean, float* coh, int64_t rows, int64_t heads, int64_t block,
+                           hipStream_t st) {
+    if (int e = check_means(who, x, ldx, mean, rows, heads, block)) return e;
+    GF_CHECK_ARG(coh, "%s: null pointer (coh)", who);
+    const int nb = (int)((rows + block - 1) / block);
+    const dim3 grid(nb, (unsigned)heads);
+    if (block == BM_QB)
+        block_means_coh_kernel<BM_QB><<<grid, BM_THREADS, 0, st>>>((const u16*)x, ldx, mean, coh, (int)rows, nb);
+    else
+        block_means_coh_kernel<BM_KB><<<grid, BM_THREADS, 0, st>>>((const u16*)x, ldx, mean, coh, (int)rows, nb);
     GF_CHECK_LAUNCH(who);
     return GF_OK;
 }
@@ -307,14 +411,25 @@ static int launch_scores(const char* who, const float* qm, const float* km, floa
 
 static int64_t select_ws_bytes(int64_t n_rows, int64_t n_words) { return align256(n_rows * 4) + align256(n_rows * n_words * 4); }
 
+// the gate of the gated entries: null coherences = that side off; the thresholds are checked by the entries
+struct Gate {
+    const float *q_coh, *k_coh;
+    float q_min, k_min;
+};
+
 static int launch_select(const char* who, const float* scores, const uint32_t* forced, int32_t* row_ptr, int32_t* tile_idx, int32_t* head_map,
-                         float* kept, void* ws, const Shape& sh, int64_t heads, float mass, hipStream_t st) {
+                         float* kept, void* ws, const Shape& sh, int64_t heads, float mass, hipStream_t st, const Gate* gate = nullptr) {
     GF_CHECK_ARG(scores && row_ptr && tile_idx && head_map && ws, "%s: null pointer", who);
     GF_CHECK_ARG(mass > 0.f, "%s: expected a mass share in (0, 1] (values above 1 select every tile), got %g", who, (double)mass);
     int32_t* counts = (int32_t*)ws;
     uint32_t* bits = (uint32_t*)((char*)ws + align256(sh.n_rows * 4));
-    block_select_kernel<<<(unsigned)sh.n_rows, BM_THREADS, 0, st>>>(scores, forced, counts, bits, kept, (int)sh.n_qb, (int)sh.n_t,
-                                                                   (int)sh.n_words, mass);
+    if (gate != nullptr && (gate->q_coh != nullptr || gate->k_coh != nullptr))
+        block_select_kernel<true><<<(unsigned)sh.n_rows, BM_THREADS, 0, st>>>(scores, forced, counts, bits, kept, (int)sh.n_qb, (int)sh.n_t,
+                                                                             (int)sh.n_words, mass, gate->q_coh, gate->k_coh, gate->q_min,
+                                                                             gate->k_min);
+    else
+        block_select_kernel<false><<<(unsigned)sh.n_rows, BM_THREADS, 0, st>>>(scores, forced, counts, bits, kept, (int)sh.n_qb, (int)sh.n_t,
+                                                                              (int)sh.n_words, mass, nullptr, nullptr, 1.f, 1.f);
     GF_CHECK_LAUNCH(who);
     block_scan_kernel<<<1, 1024, 0, st>>>(counts, row_ptr, head_map, (int)sh.n_rows, (int)heads);
     GF_CHECK_LAUNCH(who);
@@ -384,4 +499,74 @@ extern "C" GF_API int gf_block_map_from_qk(const void* q, int64_t ldq, const voi
     if (int e = launch_means(who, k, ldk, km, kv_len, heads, BM_KB, st)) return e;
     if (int e = launch_scores(who, qm, km, sc, sh, kv_len, heads, scale, st)) return e;
     return launch_select(who, sc, forced, row_ptr, tile_idx, head_map, kept, p, sh, heads, mass, st);
+}
+
+// ---------------------------------------------------------------------------------------------------- the coherence-gated entries
+static int check_gate_min(const char* who, const char* name, float v) {
+    GF_CHECK_ARG(v > 0.f && v <= 1.f, "%s: expected %s in (0, 1] (the least coherence a block is predicted for), got %g", who, name, (double)v);
+    return GF_OK;
+}
+
+extern "C" GF_API int64_t gf_block_map_gated_workspace_bytes(int64_t q_len, int64_t kv_len, int64_t heads) {
+    Shape sh;
+    if (check_shape("gf_block_map_gated_workspace_bytes", q_len, kv_len, heads, &sh) != GF_OK) return 0;
+    return align256(sh.n_rows * 128 * 4) + align256(heads * sh.n_t * 128 * 4) + align256(sh.n_rows * sh.n_t * 4) + align256(sh.n_rows * 4) +
+           align256(heads * sh.n_t * 4) + select_ws_bytes(sh.n_rows, sh.n_words);
+}
+
+extern "C" GF_API int gf_block_means_coh(const void* x, int64_t ldx, float* mean, float* coh, int64_t rows, int64_t heads, int64_t block,
+                                         void* stream) {
+    return launch_means_coh("gf_block_means_coh", x, ldx, mean, coh, rows, heads, block, (hipStream_t)stream);
+}
+
+extern "C" GF_API int gf_block_map_select_gated(const float* scores, const uint32_t* forced, const float* q_coh, const float* k_coh,
+                                                int32_t* row_ptr, int32_t* tile_idx, int32_t* head_map, float* kept, void* ws,
+                                                int64_t n_qblocks, int64_t n_tiles, int64_t heads, float mass, float q_min, float k_min,
+                                                void* stream) {
+    const char* who = "gf_block_map_select_gated";
+    GF_CHECK_ARG(n_qblocks >= 1 && heads >= 1 && heads <= 65535, "%s: expected n_qblocks >= 1 and 1 <= heads <= 65535", who);
+    GF_CHECK_ARG(n_tiles >= 2 && n_tiles <= BM_MAX_TILES, "%s: expected 2 .. 1024 key tiles, got %lld", who, (long long)n_tiles);
+    Shape sh{n_qblocks, n_tiles, heads * n_qblocks, (n_tiles + 31) / 32};
+    GF_CHECK_ARG(sh.n_rows * sh.n_t < ((int64_t)1 << 31), "%s: expected heads * n_qblocks * n_tiles below 2^31", who);
+    if (int e = check_gate_min(who, "q_min", q_min)) return e;
+    if (int e = check_gate_min(who, "k_min", k_min)) return e;
+    const Gate gate{q_coh, k_coh, q_min, k_min};
+    return launch_select(who, scores, forced, row_ptr, tile_idx, head_map, kept, ws, sh, heads, mass, (hipStream_t)stream, &gate);
+}
+
+extern "C" GF_API int gf_block_map_from_qk_gated(const void* q, int64_t ldq, const void* k, int64_t ldk, const uint32_t* forced,
+                                                 int32_t* row_ptr, int32_t* tile_idx, int32_t* head_map, float* scores, float* kept,
+                                                 float* q_coh_out, float* k_coh_out, void* ws, int64_t q_len, int64_t kv_len, int64_t heads,
+                                                 float scale, float mass, float q_min, float k_min, void* stream) {
+    const char* who = "gf_block_map_from_qk_gated";
+    Shape sh;
+    if (int e = check_shape(who, q_len, kv_len, heads, &sh)) return e;
+    GF_CHECK_ARG(ws && (((uintptr_t)ws) & 255u) == 0, "%s: expected a 256-byte aligned workspace of gf_block_map_gated_workspace_bytes bytes", who);
+    hipStream_t st = (hipStream_t)stream;
+    char* p = (char*)ws;
+    float* qm = (float*)p;
+    p += align256(sh.n_rows * 128 * 4);
+    float* km = (float*)p;
+    p += align256(heads * sh.n_t * 128 * 4);
+    float* sc = scores ? scores : (float*)p;
+    p += align256(sh.n_rows * sh.n_t * 4);
+    // a coherence output the caller asked for is written in place of the workspace's copy: the same kernel, the same bits
+    float* qc = q_coh_out ? q_coh_out : (float*)p;
+    p += align256(sh.n_rows * 4);
+    float* kc = k_coh_out ? k_coh_out : (float*)p;
+    p += align256(heads * sh.n_t * 4);
+    // every argument is checked before the first launch: a refused call enqueues nothing
+    GF_CHECK_ARG(q && k && row_ptr && tile_idx && head_map, "%s: null pointer", who);
+    GF_CHECK_ARG(ldq >= heads * 128 && ldq % 8 == 0 && gf_aligned16(q) && ldk >= heads * 128 && ldk % 8 == 0 && gf_aligned16(k),
+                 "%s: expected row strides >= heads*128 that are multiples of 8 elements and 16-byte aligned data", who);
+    GF_CHECK_ARG(scale > 0.f && scale < __builtin_inff(), "%s: the softmax scale must be positive and finite, got %g", who, (double)scale);
+    GF_CHECK_ARG(mass > 0.f, "%s: expected a mass share in (0, 1] (values above 1 select every tile), got %g", who, (double)mass);
+    // a threshold <= 0 switches its side of the gate off; NaN and values above 1 are refused
+    GF_CHECK_ARG(q_min <= 1.f, "%s: expected q_min in (0, 1], or <= 0 for no query gate, got %g", who, (double)q_min);
+    GF_CHECK_ARG(k_min <= 1.f, "%s: expected k_min in (0, 1], or <= 0 for no key gate, got %g", who, (double)k_min);
+    const Gate gate{q_min > 0.f ? qc : nullptr, k_min > 0.f ? kc : nullptr, q_min > 0.f ? q_min : 1.f, k_min > 0.f ? k_min : 1.f};
+    if (int e = launch_means_coh(who, q, ldq, qm, qc, q_len, heads, BM_QB, st)) return e;
+    if (int e = launch_means_coh(who, k, ldk, km, kc, kv_len, heads, BM_KB, st)) return e;
+    if (int e = launch_scores(who, qm, km, sc, sh, kv_len, heads, scale, st)) return e;
+    return launch_select(who, sc, forced, row_ptr, tile_idx, head_map, kept, p, sh, heads, mass, st, &gate);
 }

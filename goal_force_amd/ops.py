@@ -15,7 +15,7 @@ from ._lib import (EPI_BIAS, EPI_BIAS_GATE_RESID, EPI_BIAS_GELU_TANH, EPI_BIAS_M
                    GoalForceError)
 
 __all__ = [
-    "modulation", "layernorm_modulate", "rmsnorm_rope", "gate_residual", "gemm", "flash_attn", "flash_attn_sparse", "BlockMap", "block_means", "block_map_scores", "block_map_select", "block_map_from_qk", "patchify_im2col", "unpatchify",
+    "modulation", "layernorm_modulate", "rmsnorm_rope", "gate_residual", "gemm", "flash_attn", "flash_attn_sparse", "BlockMap", "block_means", "block_means_coherence", "block_map_scores", "block_map_select", "block_map_from_qk", "patchify_im2col", "unpatchify",
     "cfg_euler_step", "act", "add", "sub", "rel_l1", "force_map",
     "EPI_BIAS", "EPI_BIAS_GELU_TANH", "EPI_BIAS_GATE_RESID", "EPI_BIAS_RESID", "EPI_BIAS_SILU", "EPI_BIAS_MUL",
 ]
@@ -690,6 +690,29 @@ def _block_map_mass(op, mass):
     return mass
 
 
+def _block_map_min(op, name, value):
+    """A coherence threshold of the gate: None (that side off) or a number in (0, 1]."""
+    if value is None:
+        return None
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        raise GoalForceError(f"{op}.{name}: expected a number in (0, 1] (or None), got {value!r}") from None
+    if not (0.0 < v <= 1.0):
+        raise GoalForceError(f"{op}.{name}: expected 0 < {name} <= 1 (the least coherence a block is predicted for), got {v}")
+    return v
+
+
+def _block_map_coherence(op, name, t, heads, n, device):
+    """fp32 contiguous [heads, n] coherences on `device` (ops.block_means_coherence's second result)."""
+    _req(t, f"{op}.{name}", torch.float32)
+    if t.dim() != 2 or tuple(t.shape) != (heads, n) or not t.is_contiguous():
+        raise GoalForceError(f"{op}.{name}: expected contiguous [{heads}, {n}] (heads, blocks), got {tuple(t.shape)}")
+    if t.device != device:
+        raise GoalForceError(f"{op}.{name}: expected the coherences on {device}, got {t.device}")
+    return t
+
+
 def _block_map_forced(op, always, n_qb, n_t, device):
     if always is None:
         return None
@@ -728,6 +751,19 @@ def block_means(x, num_heads, block):
     return mean
 
 
+def block_means_coherence(x, num_heads, block):
+    """(mean, coh): block_means(x, num_heads, block) — the same bits — and fp32 [heads, ceil(rows / block)] coherences
+    |mean|^2 / mean(|row|^2) of the same runs (gf_block_means_coh, one pass over x): 1 for equal rows, 1/n for orthogonal rows of one
+    norm, 0 for rows that cancel, 1 for an all-zero run; NaN for non-finite input (and for finite input whose squares overflow fp32)."""
+    rows, ldx = _block_map_rows(x, "block_means_coherence.x", num_heads)
+    if block not in (SPARSE_QB, SPARSE_KB):
+        raise GoalForceError(f"block_means_coherence.block: expected {SPARSE_QB} (query blocks) or {SPARSE_KB} (key tiles), got {block!r}")
+    mean = torch.empty((num_heads, -(-rows // block), 128), dtype=torch.float32, device=x.device)
+    coh = torch.empty((num_heads, -(-rows // block)), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.load().gf_block_means_coh(_ptr(x), ldx, _ptr(mean), _ptr(coh), rows, num_heads, block, _stream(x)), "gf_block_means_coh")
+    return mean, coh
+
+
 def block_map_scores(q_mean, k_mean, q_len, kv_len, scale=None):
     """fp32 [heads, n_qblocks, n_tiles] pooled scores in the log2 domain (gf_block_map_scores): scale x log2(e) x <q_mean, k_mean> +
     log2(keys in the tile), from block_means(q, heads, 256) and block_means(k, heads, 64) of q_len queries and kv_len keys."""
@@ -745,11 +781,14 @@ def block_map_scores(q_mean, k_mean, q_len, kv_len, scale=None):
     return scores
 
 
-def block_map_select(scores, mass, always=None, want_kept=False):
+def block_map_select(scores, mass, always=None, want_kept=False, q_coherence=None, k_coherence=None, q_min=None, k_min=None):
     """The mass-cover selection and its CSR map (gf_block_map_select) from scores fp32 [heads, n_qblocks, n_tiles] (log2 domain): per
     (head, query block) the smallest top set of tiles whose share of sum 2^score reaches `mass`, `always`'s tiles forced in, at
     least 2 tiles, every tile for a row with a non-finite score or mass = 1 -> a BlockMap on the device, one map per head.
-    want_kept: (map, fp32 [heads, n_qblocks] estimated kept share)."""
+    want_kept: (map, fp32 [heads, n_qblocks] estimated kept share).
+    The coherence gate (gf_block_map_select_gated; both thresholds None: the ungated entry): with q_min, a query block whose
+    q_coherence [heads, n_qblocks] is not >= q_min selects every tile; with k_min, a tile whose k_coherence [heads, n_tiles] is not
+    >= k_min is forced for every row of its head.  A threshold and its coherences come together."""
     _req(scores, "block_map_select.scores", torch.float32)
     if scores.dim() != 3 or not scores.is_contiguous() or scores.shape[0] < 1 or scores.shape[1] < 1:
         raise GoalForceError(f"block_map_select.scores: expected contiguous [heads, n_qblocks, n_tiles], got {tuple(scores.shape)}")
@@ -757,35 +796,56 @@ def block_map_select(scores, mass, always=None, want_kept=False):
     if not 2 <= n_t <= BLOCK_MAP_MAX_TILES:
         raise GoalForceError(f"block_map_select.scores: expected 2 .. {BLOCK_MAP_MAX_TILES} key tiles, got {n_t}")
     mass = _block_map_mass("block_map_select", mass)
+    q_min, k_min = _block_map_min("block_map_select", "q_min", q_min), _block_map_min("block_map_select", "k_min", k_min)
+    for name, coh, thr, n in (("q", q_coherence, q_min, n_qb), ("k", k_coherence, k_min, n_t)):
+        if (coh is None) != (thr is None):
+            raise GoalForceError(f"block_map_select.{name}_coherence: expected {name}_coherence and {name}_min together (or neither), got "
+                                 f"{name}_coherence={'None' if coh is None else 'a tensor'}, {name}_min={thr}")
+        if coh is not None:
+            _block_map_coherence("block_map_select", f"{name}_coherence", coh, heads, n, scores.device)
     forced = _block_map_forced("block_map_select", always, n_qb, n_t, scores.device)
     lib = _lib.load()
     ws = _block_map_workspace(int(lib.gf_block_map_select_workspace_bytes(n_qb, n_t, heads)), scores.device)
     row_ptr, tile_idx, head_map = _block_map_out(heads, n_qb, n_t, scores.device)
     kept = torch.empty((heads, n_qb), dtype=torch.float32, device=scores.device) if want_kept else None
-    _lib.check(lib.gf_block_map_select(_ptr(scores), _ptr(forced), _ptr(row_ptr), _ptr(tile_idx), _ptr(head_map), _ptr(kept), _ptr(ws),
-                                       n_qb, n_t, heads, mass, _stream(scores)), "gf_block_map_select")
+    if q_min is None and k_min is None:
+        _lib.check(lib.gf_block_map_select(_ptr(scores), _ptr(forced), _ptr(row_ptr), _ptr(tile_idx), _ptr(head_map), _ptr(kept), _ptr(ws),
+                                           n_qb, n_t, heads, mass, _stream(scores)), "gf_block_map_select")
+    else:
+        # a side that is off goes as a null pointer; its threshold is then not read (1.0 passes the entry's range check)
+        _lib.check(lib.gf_block_map_select_gated(_ptr(scores), _ptr(forced), _ptr(q_coherence), _ptr(k_coherence), _ptr(row_ptr),
+                                                 _ptr(tile_idx), _ptr(head_map), _ptr(kept), _ptr(ws), n_qb, n_t, heads, mass,
+                                                 1.0 if q_min is None else q_min, 1.0 if k_min is None else k_min, _stream(scores)),
+                   "gf_block_map_select_gated")
     bm = BlockMap.from_device(row_ptr, tile_idx, head_map, heads, n_qb, n_t)
     return (bm, kept) if want_kept else bm
 
 
-def block_map_from_qk(q, k, num_heads, mass, always=None, scale=None, workspace=None, want_scores=False):
+def block_map_from_qk(q, k, num_heads, mass, always=None, scale=None, workspace=None, want_scores=False, q_min=None, k_min=None,
+                      want_coherence=False):
     """The mass-cover map of one self-attention, built on the device from its own operands (gf_block_map_from_qk: pooled means,
     pooled scores, selection, CSR — on the current stream, no host read): q [Sq, H*128], k [Skv, H*128] bf16 (row-strided views
     OK), `scale` the softmax scale the attention will use (default 1/sqrt(128)), `mass` the share of the ESTIMATED softmax mass
     every (head, query block) keeps, `always` an ops.BlockMap of one map whose tiles are kept whatever their score.  -> the
     ops.BlockMap for flash_attn_sparse (one map per head); want_scores: (map, scores fp32 [H, n_qblocks, n_tiles], estimated kept
     share fp32 [H, n_qblocks]).  `workspace`: a uint8 tensor of at least gf_block_map_workspace_bytes bytes (default: the one kept
-    per device and stream)."""
+    per device and stream).
+    q_min / k_min (numbers in (0, 1], or None): the coherence gate — gf_block_map_from_qk_gated, whose workspace is
+    gf_block_map_gated_workspace_bytes: a query block whose rows are less coherent than q_min (|mean|^2 / mean |row|^2) keeps every
+    tile, a key tile less coherent than k_min is kept by every row of its head.  want_coherence: the result is followed by
+    (q_coherence fp32 [H, n_qblocks], k_coherence fp32 [H, n_tiles]).  Both thresholds None and no want_coherence: the ungated entry."""
     sq, ldq = _block_map_rows(q, "block_map_from_qk.q", num_heads)
     skv, ldk = _block_map_rows(k, "block_map_from_qk.k", num_heads)
     if k.device != q.device:
         raise GoalForceError(f"block_map_from_qk: expected q and k on one device, got {q.device} / {k.device}")
     n_qb, n_t = _block_map_shape("block_map_from_qk", sq, skv)
     mass = _block_map_mass("block_map_from_qk", mass)
+    q_min, k_min = _block_map_min("block_map_from_qk", "q_min", q_min), _block_map_min("block_map_from_qk", "k_min", k_min)
+    gated = q_min is not None or k_min is not None or bool(want_coherence)
     scale = _sage_scale(scale)
     forced = _block_map_forced("block_map_from_qk", always, n_qb, n_t, q.device)
     lib = _lib.load()
-    nbytes = int(lib.gf_block_map_workspace_bytes(sq, skv, num_heads))
+    nbytes = int((lib.gf_block_map_gated_workspace_bytes if gated else lib.gf_block_map_workspace_bytes)(sq, skv, num_heads))
     if workspace is None:
         workspace = _block_map_workspace(nbytes, q.device)
     else:
@@ -796,11 +856,23 @@ def block_map_from_qk(q, k, num_heads, mass, always=None, scale=None, workspace=
     row_ptr, tile_idx, head_map = _block_map_out(num_heads, n_qb, n_t, q.device)
     scores = torch.empty((num_heads, n_qb, n_t), dtype=torch.float32, device=q.device) if want_scores else None
     kept = torch.empty((num_heads, n_qb), dtype=torch.float32, device=q.device) if want_scores else None
-    _lib.check(lib.gf_block_map_from_qk(_ptr(q), ldq, _ptr(k), ldk, _ptr(forced), _ptr(row_ptr), _ptr(tile_idx), _ptr(head_map),
-                                        _ptr(scores), _ptr(kept), _ptr(workspace), sq, skv, num_heads, scale, mass, _stream(q)),
-               "gf_block_map_from_qk")
+    q_coh = torch.empty((num_heads, n_qb), dtype=torch.float32, device=q.device) if want_coherence else None
+    k_coh = torch.empty((num_heads, n_t), dtype=torch.float32, device=q.device) if want_coherence else None
+    if gated:
+        # a threshold of 0 switches that side of the gate off in this entry
+        _lib.check(lib.gf_block_map_from_qk_gated(_ptr(q), ldq, _ptr(k), ldk, _ptr(forced), _ptr(row_ptr), _ptr(tile_idx), _ptr(head_map),
+                                                  _ptr(scores), _ptr(kept), _ptr(q_coh), _ptr(k_coh), _ptr(workspace), sq, skv, num_heads,
+                                                  scale, mass, 0.0 if q_min is None else q_min, 0.0 if k_min is None else k_min,
+                                                  _stream(q)), "gf_block_map_from_qk_gated")
+    else:
+        _lib.check(lib.gf_block_map_from_qk(_ptr(q), ldq, _ptr(k), ldk, _ptr(forced), _ptr(row_ptr), _ptr(tile_idx), _ptr(head_map),
+                                            _ptr(scores), _ptr(kept), _ptr(workspace), sq, skv, num_heads, scale, mass, _stream(q)),
+                   "gf_block_map_from_qk")
     bm = BlockMap.from_device(row_ptr, tile_idx, head_map, num_heads, n_qb, n_t)
-    return (bm, scores, kept) if want_scores else bm
+    out = (bm, scores, kept) if want_scores else (bm,)
+    if want_coherence:
+        out = out + (q_coh, k_coh)
+    return out if len(out) > 1 else bm
 
 
 # ---- SageAttention backend (gf_sage_attention.hip; the recipe is stated in include/goalforce.h)

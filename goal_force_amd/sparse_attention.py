@@ -95,9 +95,16 @@ class MassCover:
     attention keeps few tiles.  The mass is an ESTIMATE from pooled vectors (a Jensen lower bound of each tile's mass seen from the
     block's mean query), not a guarantee for the block's actual rows; the true retained mass of a run is 2^(lse_sparse - lse_dense)
     (tools/adaptive_map_bench.py measures it).  `keep_last`: the last built map stays as `.last_map` (tests, the bench).
-    The blocks call `from_qk(q, k, num_heads, grid, scale)`; there is no map without q and k, so `pattern(grid)` is refused."""
+    The blocks call `from_qk(q, k, num_heads, grid, scale)`; there is no map without q and k, so `pattern(grid)` is refused.
+    `q_coherence` / `k_coherence` (numbers in (0, 1], or None): the coherence gate.  A pooled mean describes its rows only when they
+    resemble each other; rho = |mean|^2 / mean(|row|^2) of a block measures that (1: equal rows).  A query block with rho below
+    q_coherence keeps every tile; a key tile with rho below k_coherence is kept by every row of its head (as an `always` tile).
+    GUARANTEED: if every ungated query block has equal rows and every unforced key tile has equal keys, every row's true retained
+    mass is >= mass (the estimate is exact on the unforced tiles and a Jensen lower bound on the forced ones; gated rows retain 1) —
+    thresholds near 1 predict only for constant blocks.  Below that, and with no gate, the mass stays an ESTIMATE to be measured;
+    incoherent data (random q, k: rho ~ 1/n) degrades the gated map to dense."""
 
-    def __init__(self, mass: float, always=None, keep_last: bool = False):
+    def __init__(self, mass: float, always=None, keep_last: bool = False, q_coherence=None, k_coherence=None):
         try:
             ok = 0.0 < float(mass) <= 1.0
         except (TypeError, ValueError):
@@ -109,10 +116,14 @@ class MassCover:
         if hasattr(always, "from_qk"):
             raise GoalForceError(f"MassCover: expected `always` to be a static pattern, got the data-dependent {always!r}")
         self.mass, self.always, self.keep_last = float(mass), always, bool(keep_last)
+        self.q_coherence = ops._block_map_min("MassCover", "q_coherence", q_coherence)
+        self.k_coherence = ops._block_map_min("MassCover", "k_coherence", k_coherence)
         self.last_map = None
 
     def __repr__(self):
-        return f"MassCover({self.mass}, always={self.always!r})"
+        if self.q_coherence is None and self.k_coherence is None:
+            return f"MassCover({self.mass}, always={self.always!r})"
+        return f"MassCover({self.mass}, always={self.always!r}, q_coherence={self.q_coherence}, k_coherence={self.k_coherence})"
 
     def __call__(self, grid, device=None):
         raise GoalForceError(f"{self!r} has no map without q and k: the blocks call from_qk(q, k, num_heads, grid, scale)")
@@ -125,7 +136,8 @@ class MassCover:
             always = self.always(_check_grid(grid))
             if not isinstance(always, ops.BlockMap):
                 raise GoalForceError(f"MassCover: expected `always` to return an ops.BlockMap, got {type(always).__name__}")
-        block_map = ops.block_map_from_qk(q, k, num_heads, self.mass, always=always, scale=scale)
+        block_map = ops.block_map_from_qk(q, k, num_heads, self.mass, always=always, scale=scale, q_min=self.q_coherence,
+                                          k_min=self.k_coherence)
         if self.keep_last:
             self.last_map = block_map
         return block_map

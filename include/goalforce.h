@@ -305,6 +305,15 @@ GF_API int gf_sumsq(const void* x, int64_t n, float* acc, void* stream);
  * line of SpargeAttn / XAttention / MInference):
  *   1. pooling   qm[h][b][:] = fp32 mean of the rows of query block b that exist (a ragged last block divides by its own count);
  *                km[h][t][:] = the same over the keys of tile t.  Sum order: a lane's rows 16 apart ascending, then a fixed tree.
+ *   1b. coherence (gf_block_means_coh, the gated entries only) of the same runs, from the same loads: rho = |m|^2 / e with m the
+ *                pooled mean above (the same sum order, the same bits as gf_block_means) and e = (sum_i |x_i|^2) / count, fp32.
+ *                0 <= rho <= 1 (Cauchy-Schwarz), rho = 1 iff the run's rows are equal, 1 - rho = the mean squared deviation from
+ *                the mean relative to the rows' energy — what makes <q_i, km> differ from <qm, km>.  e == 0 (all rows zero, hence
+ *                equal) gives rho = 1.  Sum order of e: per lane the chain e = fma(x, x, e) over the row's 8 channels, rows 16 apart
+ *                ascending; the 16 channel-group lanes by xor 1, 2, 4, 8; then the means' tree (row groups xor 1, 2; waves 0 .. 3);
+ *                / count.  |m|^2: lane l forms fma(m[l + 64], m[l + 64], m[l] * m[l]), then xor 1, 2, .. 32.  No atomics.
+ *                Non-finite input gives NaN; so does FINITE input whose squares overflow fp32 (|x| beyond ~1e19) — conservative:
+ *                NaN counts as incoherent below.
  *   2. scores    s[h][b][t] = fma(c, dot, log2(n_keys(t))), dot = fma chain over d = 0 .. 127, c = fp32(double(scale) * log2(e))
  *                (the package's pre-scaled q with scale = ln 2 gives c = 1); n_keys(t) = 64, or the ragged last tile's count.
  *                By Jensen's inequality n_keys 2^dot-term is a LOWER bound of the tile's true unnormalised mass seen from the pooled
@@ -316,6 +325,11 @@ GF_API int gf_sumsq(const void* x, int64_t n, float* acc, void* stream);
  *                Fewer than 2 selected: the largest unselected w is added (lowest index on ties) until there are 2.  mass >= 1
  *                selects every tile.  A row with ANY non-finite score selects every tile — so every emitted row is valid (>= 2
  *                ascending indices < n_t) for any input bits.  All sums are fp32 in one fixed order.
+ *                The gate (gf_block_map_select_gated): a row (h, b) with !(q_coh[h][b] >= q_min) selects every tile, as a row with a
+ *                non-finite score does (kept = 1); a tile t with !(k_coh[h][t] >= k_min) is forced for every row of head h — OR-ed
+ *                with `forced`, counted in F, under the same rules (forced only when F >= mass * W, the two-tile floor).  Written
+ *                `!(rho >= min)` so that a NaN coherence fires.  q_coh fp32 [heads][n_qb], k_coh fp32 [heads][n_t]; NULL switches
+ *                that side off, both NULL are the bits of gf_block_map_select.  q_min, k_min in (0, 1] (else refused by name).
  *   4. emit      row_ptr int32 [heads * n_qb + 1] (row_ptr[0] = 0, a scan of the counts on the device), tile_idx int32 ascending
  *                inside a row, caller-owned with capacity heads * n_qb * n_t (the worst case), head_map int32 [heads] = 0 .. heads-1;
  *                the sparse kernel takes them with n_maps = heads.
@@ -324,7 +338,20 @@ GF_API int gf_sumsq(const void* x, int64_t n, float* acc, void* stream);
  * No atomics: two calls on the same operands write the same bits; gf_block_map_from_qk writes the bits of the staged calls
  * (gf_block_means x 2, gf_block_map_scores, gf_block_map_select), which it runs on `stream` in that order.
  *   ws of gf_block_map_from_qk: gf_block_map_workspace_bytes bytes, 256-byte aligned (qm, km, scores, the selection's scratch);
- *   ws of gf_block_map_select: gf_block_map_select_workspace_bytes bytes (counts and selection bitmasks).  One per stream in flight. */
+ *   ws of gf_block_map_select: gf_block_map_select_workspace_bytes bytes (counts and selection bitmasks).  One per stream in flight.
+ * The gated entries (coherence, step 1b, and the gate of step 3) change none of the above: the ungated entries write the bits they
+ * wrote before.  gf_block_map_from_qk_gated runs gf_block_means_coh x 2 (in place of the pooling pass: q and k are still read once
+ * each), gf_block_map_scores, gf_block_map_select_gated on `stream`, checks every argument before the first launch and writes the
+ * bits of those staged calls; q_coh_out fp32 [heads][n_qb] / k_coh_out fp32 [heads][n_t] receive the coherences (NULL to skip);
+ * q_min <= 0 / k_min <= 0 switches that side of the gate off there (NaN and values above 1 are refused); ws:
+ * gf_block_map_gated_workspace_bytes bytes, 256-byte aligned; gf_block_map_select_gated takes gf_block_map_select's workspace.
+ * What the gate GUARANTEES.  Assume every ungated query block has equal rows and every unforced key tile has equal keys.  Then for a
+ * row of an ungated block the pooled query IS the row, the estimate n 2^dot-term is exact on the unforced tiles and a lower bound
+ * (Jensen) on the forced ones.  With S the exact mass of the selected unforced tiles, U that of the unselected tiles, F_true >= F_est
+ * the true and the estimated mass of the forced tiles, the retained share is (F_true + S) / (F_true + S + U) >= (F_est + S) /
+ * (F_est + S + U) >= mass, because x / (x + U) increases in x; gated rows retain 1.  So thresholds near 1 predict only for constant
+ * blocks and the promise holds; no gate uses the pooled estimate everywhere; in between the true retained mass is MEASURED
+ * (2^(lse_sparse - lse_dense)), not promised. */
 GF_API int64_t gf_block_map_workspace_bytes(int64_t q_len, int64_t kv_len, int64_t heads);     /* 0: a shape the entry refuses */
 GF_API int64_t gf_block_map_select_workspace_bytes(int64_t n_qblocks, int64_t n_tiles, int64_t heads);
 /* mean fp32 [heads][ceil(rows / block)][128]; block = 256 (query blocks) or 64 (key tiles) */
@@ -336,6 +363,17 @@ GF_API int gf_block_map_select(const float* scores, const uint32_t* forced, int3
 GF_API int gf_block_map_from_qk(const void* q, int64_t ldq, const void* k, int64_t ldk, const uint32_t* forced, int32_t* row_ptr,
                                 int32_t* tile_idx, int32_t* head_map, float* scores, float* kept, void* ws, int64_t q_len,
                                 int64_t kv_len, int64_t heads, float scale, float mass, void* stream);
+GF_API int64_t gf_block_map_gated_workspace_bytes(int64_t q_len, int64_t kv_len, int64_t heads);       /* 0: a shape the entry refuses */
+/* gf_block_means plus coh fp32 [heads][ceil(rows / block)]; refuses what gf_block_means refuses, and a null coh */
+GF_API int gf_block_means_coh(const void* x, int64_t ldx, float* mean, float* coh, int64_t rows, int64_t heads, int64_t block,
+                              void* stream);
+GF_API int gf_block_map_select_gated(const float* scores, const uint32_t* forced, const float* q_coh, const float* k_coh,
+                                     int32_t* row_ptr, int32_t* tile_idx, int32_t* head_map, float* kept, void* ws, int64_t n_qblocks,
+                                     int64_t n_tiles, int64_t heads, float mass, float q_min, float k_min, void* stream);
+GF_API int gf_block_map_from_qk_gated(const void* q, int64_t ldq, const void* k, int64_t ldk, const uint32_t* forced, int32_t* row_ptr,
+                                      int32_t* tile_idx, int32_t* head_map, float* scores, float* kept, float* q_coh_out,
+                                      float* k_coh_out, void* ws, int64_t q_len, int64_t kv_len, int64_t heads, float scale, float mass,
+                                      float q_min, float k_min, void* stream);
 
 /* ------------------------------------------------------------------------
  * gf_patchify_im2col — gathers the (1,2,2) patches of an NCTHW latent into a
