@@ -6,7 +6,8 @@ lengths around the 64-key tile and the 2048-key kernel switch, strided operands 
 GEMM epilogue, in-place residuals — and reports every case whose error exceeds the operator's bar, or whose call fails without being a
 refusal the header documents.  Exit code 1 when anything failed.  `--only fwdrows` (not part of the default sweep) holds the forward
 row kernels against the exact chains of tests/forward_refs.py, `--only attnfwd` (opt-in as well) the attention forward's entry points
-against the bounds of tests/attention_fwd_refs.py."""
+against the bounds of tests/attention_fwd_refs.py, `--only gemmpin` (opt-in) the GEMM family against the exact chain and the two bars
+of tests/gemm_refs.py."""
 import argparse
 import math
 import os
@@ -417,9 +418,70 @@ def case_attnfwd(rnd, g):
     return f"attnfwd {entry} q={sq} kv={skv} heads={heads} {name} mult={mult} maps={lists}", err, 1.0
 
 
-CASES = {"gemm": case_gemm, "attn": case_attn, "rows": case_rows, "cfg": case_cfg, "attnbwd": case_attnbwd, "fp8": case_fp8,
+def case_gemmpin(rnd, g):
+    """The GEMM family pinned as tests/test_gemm_pinned_gpu.py pins it (helpers: tests/gemm_refs.py), at random shapes: gf_gemm_bf16 /
+    gf_gemm_fp8 on a random kernel form (M on either side of 512, prefer_8wave, a4_stagger 0 .. 3, a4_group_m), a random epilogue, A
+    as a column slice (lda > K), C as a column slice of a wider buffer or aliasing resid, one of the three data classes.  integers /
+    selector: any differing bit is an error (the activations: gf_act of the exact Linear, -0 on the header's tails); gauss: err = the
+    largest of the differing share over 2^-10 (any differing element below 1024 elements), the worst row / column count over its
+    binomial cap and the worst element's share of 2^-7 m + L (K 2^-23 S + T); bar 1."""
+    if os.path.join(ROOT, "tests") not in sys.path:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import gemm_refs as R
+    fp8 = rnd.random() < 0.4
+    cls = rnd.choice(["integers", "selector", "gauss"])
+    M = rnd.choice([1, 15, 16, 17, 63, 64, 65, 127, 128, 129, 255, 256, 257, 511, 512, 513, 527, 640, 641, 769, 1025, rnd.randrange(1, 1200)])
+    N = 8 * rnd.choice([1, 2, 3, 15, 16, 17, 31, 32, 33, 65, 97, rnd.randrange(1, 100)])
+    K = (128 if fp8 else 64) * rnd.choice([1, 2, 3, 4, 5, 8] if cls != "integers" else [1, 2, 3, 5])
+    epi = rnd.choice(R.EPIS)
+    opts = dict(prefer_8wave=int(rnd.random() < 0.3), a4_stagger=rnd.choice([0, 1, 2, 2, 3]), a4_group_m=rnd.choice([0, 0, 4, 8]))
+    d = R.INPUTS[cls](M, N, K, seed=rnd.randrange(1000), fp8=fp8)
+    if cls == "gauss" and fp8:                     # the operands the product path feeds the kernel: the device's own quantisers
+        x8, sc = ops.quant_fp8_rowscale(d["x"].cuda())
+        w8 = ops.cast_fp8(d["w_bf16"].cuda())
+        dq = dict(d, a=x8.view(torch.uint8).cpu(), w=w8.view(torch.uint8).cpu(), rs=sc.cpu())
+        assert all(torch.equal(d[k], dq[k]) for k in ("a", "w", "rs")), "the device quantisers do not give the codes of gemm_refs' stand-in"
+        d = dq
+    lal = 16 if fp8 else 8
+    extra = lal * rnd.choice([0, 0, 1, 4])
+    a_full = torch.zeros((M, K + extra), dtype=d["a"].dtype, device="cuda")
+    a_full[:, :K] = d["a"].cuda()
+    a = a_full[:, :K]
+    w = d["w"].cuda()
+    if fp8:
+        a, w = a.view(torch.float8_e4m3fn), w.view(torch.float8_e4m3fn)
+    dev = {k: None if d[k] is None else d[k].cuda() for k in ("bias", "resid", "gate", "rs")}
+    need_r = epi in (R.EPI_GATE_RESID, R.EPI_RESID, R.EPI_MUL)
+    resid, out, how = (dev["resid"] if need_r else None), None, "plain"
+    if need_r and rnd.random() < 0.3:              # C aliases resid
+        resid = out = dev["resid"].clone()
+        how = "in place"
+    elif rnd.random() < 0.4:                       # C is a column slice of a wider buffer
+        off = 8 * rnd.choice([0, 1, 3])
+        big = torch.zeros((M, N + off + 8), dtype=BF, device="cuda")
+        out, how = big[:, off:off + N], f"ldc {N + off + 8}"
+    kw = dict(epilogue=epi, resid=resid, gate=dev["gate"] if epi == R.EPI_GATE_RESID else None, out=out)
+    with ops.options(**opts):
+        got = ops.gemm_fp8(a, dev["rs"], w, dev["bias"], **kw) if fp8 else ops.gemm(a, w, dev["bias"], **kw)
+    torch.cuda.synchronize()
+    got = got.cpu()
+    ref = R.reference(d, epi)
+    desc = f"gemmpin {'fp8' if fp8 else 'bf16'} {cls} M={M} N={N} K={K} {R.EPI_NAMES[epi]} lda+{extra} {how} {opts}"
+    if cls == "gauss":
+        j = R.judge(got, ref, K)
+        a_err = (math.inf if j["differing"] else 0.0) if R.SHARE_CAP * j["numel"] < 1 else j["share"] / R.SHARE_CAP
+        return desc + " | " + R.describe(j), max(a_err, j["row_worst"] / j["row_cap"], j["col_worst"] / j["col_cap"], j["worst"]), 1.0
+    want = ref.out.to(BF)
+    if epi in (R.EPI_GELU, R.EPI_SILU):            # a function of the exact bf16 y: gf_act's bits, -0 on the header's tail
+        y = R.reference(d, R.EPI_BIAS).out.to(BF)
+        want = torch.where(R.tail_mask(y, epi), torch.full_like(y, -0.0), ops.act(y.cuda(), "gelu_tanh" if epi == R.EPI_GELU else "silu").cpu())
+    differing = int((R.bits(got) != R.bits(want)).sum())
+    return desc + f" | {differing} elements differ", (math.inf if differing else 0.0), 1.0
+
+
+CASES = {"gemmpin": case_gemmpin, "gemm": case_gemm, "attn": case_attn, "rows": case_rows, "cfg": case_cfg, "attnbwd": case_attnbwd, "fp8": case_fp8,
          "batched": case_batched, "misc": case_misc, "bwdrows": case_bwdrows, "fwdrows": case_fwdrows, "attnfwd": case_attnfwd}
-OPT_IN = ("fwdrows", "attnfwd")       # run with --only alone (bwdrows is in the default sweep): the default sweep, and the suite's run of it, stays what it was
+OPT_IN = ("fwdrows", "attnfwd", "gemmpin")       # run with --only alone (bwdrows is in the default sweep): the default sweep, and the suite's run of it, stays what it was
 
 
 def main():
