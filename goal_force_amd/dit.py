@@ -10,6 +10,7 @@ Activations are token-major [S, D] bf16 (batch 1 per call on the hot path; B > 1
 """
 from __future__ import annotations
 
+import functools
 import math
 from typing import Optional, Tuple
 
@@ -174,16 +175,22 @@ class QuantizedInput:
         return self.x8.is_cuda
 
 
+def fp8_weight(lin: nn.Linear):
+    """The layer's current e4m3 weight copy (enable_fp8), or None for a bf16 layer."""
+    w8 = getattr(lin, "_gf_w8", None)
+    if w8 is not None and lin._gf_w8_key != param_key(lin.weight):          # the bf16 master changed since the cast: refresh the copy
+        w8 = lin._gf_w8 = ops.cast_fp8(lin.weight.detach().contiguous())
+        lin._gf_w8_key = param_key(lin.weight)
+    return w8
+
+
 def linear(x2, lin: nn.Linear, epilogue=ops.EPI_BIAS, resid=None, gate=None, out=None):
     """One nn.Linear on the MFMA GEMM.  If the layer carries an fp8 weight copy (enable_fp8) the reference's
     fp8_linear contract is used (VRAM:115-151: per-row dynamic activation scale, unit weight scale, e4m3),
     otherwise the bf16 kernel.  x2 may be a QuantizedInput to reuse one quantisation for several layers."""
-    w8 = getattr(lin, "_gf_w8", None)
+    w8 = fp8_weight(lin)
     if w8 is None:
         return ops.gemm(x2, lin.weight, lin.bias, epilogue=epilogue, resid=resid, gate=gate, out=out)
-    if lin._gf_w8_key != param_key(lin.weight):          # the bf16 master changed since the cast: refresh the copy
-        w8 = lin._gf_w8 = ops.cast_fp8(lin.weight.detach().contiguous())
-        lin._gf_w8_key = param_key(lin.weight)
     q = x2 if isinstance(x2, QuantizedInput) else QuantizedInput(x2)
     return ops.gemm_fp8(q.x8, q.scale, w8, lin.bias, epilogue=epilogue, resid=resid, gate=gate, out=out)
 
@@ -199,7 +206,6 @@ def enable_fp8(module: nn.Module, enabled=True):
                     lin._gf_w8 = ops.cast_fp8(lin.weight.detach().contiguous()) if enabled else None
                     lin._gf_w8_key = param_key(lin.weight) if enabled else None
     return module
-
 
 
 def enable_sage_attention(module: nn.Module, enabled=True):
@@ -238,6 +244,50 @@ def enable_sparse_attention(module: nn.Module, pattern, dense_blocks: int = 0):
         if isinstance(blk, DiTBlock) and id(blk) not in in_stack:       # a block handed over on its own
             blk.self_attn._gf_sparse = pattern
     return module
+
+
+def refuse_training(block: "DiTBlock"):
+    """What training.DiTBlockFn refuses of a block's switches, before its forward runs."""
+    if any(getattr(m, "_gf_w8", None) is not None for m in block.modules()):
+        # the backward recomputes the block on the bf16 kernels: an fp8 forward would not be the function differentiated
+        raise GoalForceError("training through an enable_fp8 block is refused: call enable_fp8(module, False) first")
+    if getattr(block.self_attn, "_gf_sage", False):
+        # no backward exists for the sage backend (nor in the sageattention package): the backward would differentiate another function
+        raise GoalForceError("training through a block with enable_sage_attention is refused: call enable_sage_attention(module, False) first")
+    if getattr(block.self_attn, "_gf_sparse", None) is not None:
+        # there is no sparse backward: the backward recomputes and differentiates the DENSE attention, whatever the keep level
+        # (with keep level "none" the forward's own refusal, SelfAttention.attention_backend(keep=...), is never reached)
+        raise GoalForceError("training through a block with enable_sparse_attention is refused (there is no sparse backward): "
+                             "call enable_sparse_attention(module, None) first")
+
+
+def q_rotation(rope: RopeTable, head_dim: int, prescale: bool):
+    """(q_cos, q_sin, attn_scale) of the self-attention's q: SelfAttention.attend, and training.DiTBlockFn.backward with the
+    `prescale` (ops.options(attn_q_prescale)) its forward saw.
+    Q leaves its RMSNorm + RoPE kernel already multiplied by c = softmax scale x log2(e) (the rotation table carries the factor:
+    RopeTable.scaled), and the attention is called with scale = ln 2, i.e. c = 1 inside — its `Q <- bf16(Q c)` is then exact.
+    One rounding of the rotated q instead of two: at peaky logits (std 3) the self-attention kernel is 3.9e-3 from fp64 on a
+    twice-rounded Q and at torch SDPA's level (1.8e-3) on this one (tools/fuzz_ops.py, profiles/r06).  Training too (`keep`):
+    the backward rebuilds P from q.k and the forward's log-sum-exp, and a forward that rounded Q a second time hands it an lse
+    of OTHER scores — rows of P off by 2^-9 of the logit, dQ / dK / dV 1.7e-2 from fp64 at logit std 8 where torch's SDPA
+    backward is at 4e-3 (tools/attnbwd_precision.py).  On the pre-scaled q forward and backward see the same scores; the
+    backward of the norm + rotation takes the same scaled table (training.DiTBlockFn) and so returns d/d(projection)."""
+    if not prescale:
+        return rope.cos, rope.sin, None
+    return (*rope.scaled(Q_PRESCALE(head_dim)), math.log(2.0))
+
+
+def _checked_map(block_map) -> ops.BlockMap:
+    if not isinstance(block_map, ops.BlockMap):
+        raise GoalForceError(f"sparse attention: expected the pattern to return an ops.BlockMap, got {type(block_map).__name__}")
+    return block_map
+
+
+def _sparse_attn_from_qk(pattern, grid, q, k, v, num_heads, vt=None, scale=None):
+    """A data-dependent pattern (sparse_attention.MassCover): the map is built from the finished q and k — after norm + RoPE and
+    the pre-scaling — with the scale the attention itself gets, on the same stream."""
+    block_map = _checked_map(pattern.from_qk(q, k, num_heads, grid, scale))
+    return ops.flash_attn_sparse(q, k, v, num_heads, block_map, vt=vt, scale=scale)
 
 
 def sageattn(q, k, v, tensor_layout="HND", is_causal=False, sm_scale=None, return_lse=False, **kw):
@@ -313,6 +363,38 @@ class SelfAttention(nn.Module):
         self.q, self.k, self.v, self.o = (nn.Linear(dim, dim) for _ in range(4))
         self.norm_q, self.norm_k = RMSNorm(dim, eps=eps), RMSNorm(dim, eps=eps)
 
+    def attention_backend(self, rope: RopeTable, tokens: int, sp, keep, dense: bool):
+        """The attention this call runs, attn(q, k, v, num_heads, vt=None, scale=None): ops.flash_attn, ops.sage_attn, or — a block
+        switched by enable_sparse_attention, unless `dense` — ops.flash_attn_sparse on the pattern's map of rope.grid, built here (a
+        static pattern) or per call (from_qk).  Every refusal comes before the first kernel: a switched block never falls back to
+        the dense path on its own."""
+        sage = getattr(self, "_gf_sage", False)
+        if sage and keep is not None:
+            raise GoalForceError("training through a block with enable_sage_attention is refused (the sage backend has no backward): "
+                                 "call enable_sage_attention(module, False) first")
+        pattern = getattr(self, "_gf_sparse", None)
+        if pattern is None or dense:
+            return ops.sage_attn if sage else ops.flash_attn
+        if sage:
+            raise GoalForceError("sparse attention with enable_sage_attention is refused (the sage kernel takes no block map): switch one off")
+        if keep is not None:
+            raise GoalForceError("training through a block with enable_sparse_attention is refused (there is no sparse backward): "
+                                 "call enable_sparse_attention(module, None) first")
+        if sp is not None:
+            raise GoalForceError("sparse attention under sequence parallelism is refused (the head-parallel exchange takes no block map)")
+        grid = getattr(rope, "grid", None)
+        if grid is None:
+            raise GoalForceError("sparse attention needs the token grid: expected a RopeTable built by WanModel.rope_table "
+                                 "(RopeTable.from_grid), got rotary phases without one")
+        if tokens != grid[0] * grid[1] * grid[2]:
+            raise GoalForceError(f"sparse attention: expected {grid[0] * grid[1] * grid[2]} tokens for the grid {grid}, got {tokens}")
+        if tokens < ops.VT_MIN_KV:
+            raise GoalForceError(f"sparse attention: expected at least {ops.VT_MIN_KV} tokens (ops.VT_MIN_KV, where the self-attention "
+                                 f"runs on kernel 3), got {tokens}")
+        if hasattr(pattern, "from_qk"):
+            return functools.partial(_sparse_attn_from_qk, pattern, grid)
+        return functools.partial(ops.flash_attn_sparse, block_map=_checked_map(pattern(grid)).to(rope.cos.device))
+
     def attend(self, x2: torch.Tensor, rope: RopeTable, sp=None, keep=None, dense=False) -> torch.Tensor:
         """x2 [S,D] -> attention output BEFORE the o projection, [S,D].  With a sequence_parallel.SequenceParallel
         group `sp`, x2 and rope are this rank's token chunk and the heads are exchanged over xGMI (usp_attn_forward,
@@ -320,97 +402,64 @@ class SelfAttention(nn.Module):
         rows' log-sum-exp are stored under "attn" / "lse" so that the backward does not run the attention again; with
         keep["wide"] also the three projections ("qp", "kp" before their norm, "v").  `dense`: a block switched by
         enable_sparse_attention attends densely in this call (pipe.sparse_dense_steps)."""
+        attn = self.attention_backend(rope, x2.shape[0], sp, keep, dense)
         fp8 = getattr(self.q, "_gf_w8", None) is not None
-        sage = getattr(self, "_gf_sage", False)
-        if sage and keep is not None:
-            raise GoalForceError("training through a block with enable_sage_attention is refused (the sage backend has no backward): "
-                                 "call enable_sage_attention(module, False) first")
-        attn = ops.sage_attn if sage else ops.flash_attn
-        pattern = getattr(self, "_gf_sparse", None)
-        if pattern is not None and not dense:
-            # every refusal comes before the first kernel: a switched block never falls back to the dense path on its own
-            if sage:
-                raise GoalForceError("sparse attention with enable_sage_attention is refused (the sage kernel takes no block map): switch one off")
-            if keep is not None:
-                raise GoalForceError("training through a block with enable_sparse_attention is refused (there is no sparse backward): "
-                                     "call enable_sparse_attention(module, None) first")
-            if sp is not None:
-                raise GoalForceError("sparse attention under sequence parallelism is refused (the head-parallel exchange takes no block map)")
-            grid = getattr(rope, "grid", None)
-            if grid is None:
-                raise GoalForceError("sparse attention needs the token grid: expected a RopeTable built by WanModel.rope_table "
-                                     "(RopeTable.from_grid), got rotary phases without one")
-            if x2.shape[0] != grid[0] * grid[1] * grid[2]:
-                raise GoalForceError(f"sparse attention: expected {grid[0] * grid[1] * grid[2]} tokens for the grid {grid}, got {x2.shape[0]}")
-            if x2.shape[0] < ops.VT_MIN_KV:
-                raise GoalForceError(f"sparse attention: expected at least {ops.VT_MIN_KV} tokens (ops.VT_MIN_KV, where the self-attention "
-                                     f"runs on kernel 3), got {x2.shape[0]}")
-            if hasattr(pattern, "from_qk"):
-                # a data-dependent pattern (sparse_attention.MassCover): the map is built from the finished q and k — after norm +
-                # RoPE and the pre-scaling — with the scale the attention itself gets, on the same stream
-                def attn(q, k, v, num_heads, vt=None, scale=None):
-                    block_map = pattern.from_qk(q, k, num_heads, grid, scale)
-                    if not isinstance(block_map, ops.BlockMap):
-                        raise GoalForceError(f"sparse attention: expected the pattern to return an ops.BlockMap, got {type(block_map).__name__}")
-                    return ops.flash_attn_sparse(q, k, v, num_heads, block_map, vt=vt, scale=scale)
-            else:
-                block_map = pattern(grid)
-                if not isinstance(block_map, ops.BlockMap):
-                    raise GoalForceError(f"sparse attention: expected the pattern to return an ops.BlockMap, got {type(block_map).__name__}")
-                block_map = block_map.to(rope.cos.device)
+        xin = (x2 if isinstance(x2, QuantizedInput) else QuantizedInput(x2)) if fp8 else x2      # one quantisation for the three projections
+        q_rot = q_rotation(rope, self.head_dim, ops.option("attn_q_prescale"))
+        if keep is not None:
+            return self._attend_keep(xin, rope, q_rot, keep, sp)
+        if sp is not None:
+            return self._attend_head_parallel(xin, rope, q_rot, sp, "sage" if attn is ops.sage_attn else "flash")
+        q, k = self._qk(xin, rope, q_rot, None)
+        vt = self._vt_from_projection(xin)
+        v = linear(xin, self.v) if vt is None else None
+        return attn(q, k, v, self.num_heads, vt=vt, scale=q_rot[2])
 
-                def attn(q, k, v, num_heads, vt=None, scale=None):
-                    return ops.flash_attn_sparse(q, k, v, num_heads, block_map, vt=vt, scale=scale)
-        xin = (x2 if isinstance(x2, QuantizedInput) else QuantizedInput(x2)) if fp8 else x2
-        # Q leaves its RMSNorm + RoPE kernel already multiplied by c = softmax scale x log2(e) (the rotation table carries the factor:
-        # RopeTable.scaled), and the attention is called with scale = ln 2, i.e. c = 1 inside — its `Q <- bf16(Q c)` is then exact.
-        # One rounding of the rotated q instead of two: at peaky logits (std 3) the self-attention kernel is 3.9e-3 from fp64 on a
-        # twice-rounded Q and at torch SDPA's level (1.8e-3) on this one (tools/fuzz_ops.py, profiles/r06).  Training too (`keep`):
-        # the backward rebuilds P from q.k and the forward's log-sum-exp, and a forward that rounded Q a second time hands it an lse
-        # of OTHER scores — rows of P off by 2^-9 of the logit, dQ / dK / dV 1.7e-2 from fp64 at logit std 8 where torch's SDPA
-        # backward is at 4e-3 (tools/attnbwd_precision.py).  On the pre-scaled q forward and backward see the same scores; the
-        # backward of the norm + rotation takes the same scaled table (training.DiTBlockFn) and so returns d/d(projection).
-        q_cos, q_sin, attn_scale = rope.cos, rope.sin, None
-        if ops._OPT["attn_q_prescale"]:
-            (q_cos, q_sin), attn_scale = rope.scaled(Q_PRESCALE(self.head_dim)), math.log(2.0)
-        if sp is not None and keep is None:
-            # head-parallel: every projection's tokens-for-heads exchange starts as soon as the projection is ready and flies under
-            # the next one (same kernels on the same values as below: bit-identical, another issue order)
-            k = linear(xin, self.k)
-            ops.rmsnorm_rope(k, self.norm_k.weight, rope.cos, rope.sin, self.head_dim, self.norm_k.eps)
-            hk = sp.heads_start(k, self.num_heads)
-            hv = sp.heads_start(linear(xin, self.v), self.num_heads)
-            q = linear(xin, self.q)
-            ops.rmsnorm_rope(q, self.norm_q.weight, q_cos, q_sin, self.head_dim, self.norm_q.eps)
-            hq = sp.heads_start(q, self.num_heads)
-            return sp.attention_started(hq, hk, hv, self.num_heads, tuple(q.shape), scale=attn_scale, backend="sage" if sage else "flash")
+    def _qk(self, xin, rope, q_rot, keep):
+        """The q and k projections, normed and rotated in place (q with the table of q_rotation)."""
         q, k = linear(xin, self.q), linear(xin, self.k)
         if keep is not None and keep.get("wide"):      # training with room to spare: the pre-norm projections stay for the backward
             keep["qp"], keep["kp"] = q, k
             q, k = q.clone(), k.clone()
-        ops.rmsnorm_rope(q, self.norm_q.weight, q_cos, q_sin, self.head_dim, self.norm_q.eps)
+        ops.rmsnorm_rope(q, self.norm_q.weight, q_rot[0], q_rot[1], self.head_dim, self.norm_q.eps)
         ops.rmsnorm_rope(k, self.norm_k.weight, rope.cos, rope.sin, self.head_dim, self.norm_k.eps)
-        if sp is None and keep is None and not fp8 and x2.is_cuda and self.v.weight.shape[0] >= 512 \
-                and ops.vt32_ok(x2.shape[0], self.num_heads, self.head_dim):
-            # inference on one GPU: nothing but the attention reads V, so the projection writes it straight in the layout the
-            # attention kernel wants (gf_linear_vt32: same bits as the plain projection + the transpose, one pass over V less)
-            return attn(q, k, None, self.num_heads, vt=ops.linear_vt32(x2, self.v.weight, self.v.bias), scale=attn_scale)
-        if sp is None and keep is None and fp8 and xin.is_cuda and self.v.weight.shape[0] >= 512 and self.v.weight.shape[1] % 128 == 0 \
-                and ops.vt32_ok(xin.shape[0], self.num_heads, self.head_dim):
-            # config 5 on one GPU: the fp8 V projection writes the attention kernel's V^T operand as well (gf_linear_vt32_fp8)
-            if self.v._gf_w8_key != param_key(self.v.weight):
-                self.v._gf_w8 = ops.cast_fp8(self.v.weight.detach().contiguous())
-                self.v._gf_w8_key = param_key(self.v.weight)
-            return attn(q, k, None, self.num_heads, vt=ops.linear_vt32_fp8(xin.x8, xin.scale, self.v._gf_w8, self.v.bias), scale=attn_scale)
+        return q, k
+
+    def _vt_from_projection(self, xin):
+        """Inference on one GPU (attend calls this with neither `sp` nor `keep`): nothing but the attention reads V, so the projection
+        writes it straight in the layout the attention kernel wants (gf_linear_vt32: same bits as the plain projection + the
+        transpose, one pass over V less; config 5: gf_linear_vt32_fp8).  -> the V^T operand, or None where the plain projection runs."""
+        w = self.v.weight
+        fp8 = isinstance(xin, QuantizedInput)
+        if not xin.is_cuda or w.shape[0] < 512 or (fp8 and w.shape[1] % 128) or not ops.vt32_ok(xin.shape[0], self.num_heads, self.head_dim):
+            return None
+        if fp8:
+            return ops.linear_vt32_fp8(xin.x8, xin.scale, fp8_weight(self.v), self.v.bias)
+        return ops.linear_vt32(xin, w, self.v.bias)
+
+    def _attend_head_parallel(self, xin, rope, q_rot, sp, backend):
+        """Head-parallel inference: every projection's tokens-for-heads exchange starts as soon as the projection is ready and flies
+        under the next one (same kernels on the same values as the plain path: bit-identical, another issue order)."""
+        k = linear(xin, self.k)
+        ops.rmsnorm_rope(k, self.norm_k.weight, rope.cos, rope.sin, self.head_dim, self.norm_k.eps)
+        hk = sp.heads_start(k, self.num_heads)
+        hv = sp.heads_start(linear(xin, self.v), self.num_heads)
+        q = linear(xin, self.q)
+        ops.rmsnorm_rope(q, self.norm_q.weight, q_rot[0], q_rot[1], self.head_dim, self.norm_q.eps)
+        hq = sp.heads_start(q, self.num_heads)
+        return sp.attention_started(hq, hk, hv, self.num_heads, tuple(q.shape), scale=q_rot[2], backend=backend)
+
+    def _attend_keep(self, xin, rope, q_rot, keep, sp):
+        """Training: the plain projections, the attention with its log-sum-exp, and what the backward asked to keep.  (Always the
+        flash backend: attention_backend refuses `keep` on every other.)"""
+        q, k = self._qk(xin, rope, q_rot, keep)
         v = linear(xin, self.v)
         if sp is not None:
-            return sp.attention(q, k, v, self.num_heads, scale=attn_scale, backend="sage" if sage else "flash")
-        if keep is not None:
-            keep["attn"], keep["lse"] = ops.flash_attn_lse(q, k, v, self.num_heads, scale=attn_scale)
-            if keep.get("wide"):
-                keep["v"] = v
-            return keep["attn"]
-        return attn(q, k, v, self.num_heads, scale=attn_scale)
+            return sp.attention(q, k, v, self.num_heads, scale=q_rot[2], backend="flash")
+        keep["attn"], keep["lse"] = ops.flash_attn_lse(q, k, v, self.num_heads, scale=q_rot[2])
+        if keep.get("wide"):
+            keep["v"] = v
+        return keep["attn"]
 
     def forward(self, x, freqs):
         x2 = _tokens2d(x)
@@ -442,7 +491,7 @@ class CrossAttention(nn.Module):
         of one host read-back per block).  `ops.options(fold_pad_keys=False)` switches the folding off (A/B, and the cross-check in
         tests/test_kernels_gpu.py)."""
         m = 1
-        if fold and ctx2.is_cuda and ops._OPT["fold_pad_keys"]:
+        if fold and ctx2.is_cuda and ops.option("fold_pad_keys"):
             n = pad_run(ctx2) if pad_n is None else pad_n
             if ctx2.shape[0] - n >= 2 and n + 1 < ops.VT_MIN_KV:      # (the multiplicity form exists for short key sequences only)
                 m = ctx2.shape[0] - n
@@ -469,7 +518,7 @@ class CrossAttention(nn.Module):
         """Does the folded path serve this (inference) forward: pad-folded keys (multiplicity > 1) few enough for one key tile,
         a bf16 o projection (not the fp8_linear contract), no autograd, a GEMM-able K (heads x n_pad a multiple of 64: not the
         2-head test models), ops.options(fold_cross_o) on."""
-        if not ops._OPT["fold_cross_o"] or torch.is_grad_enabled() or len(kv) < 3 or kv[2] == 1 or self.head_dim != 128:
+        if not ops.option("fold_cross_o") or torch.is_grad_enabled() or len(kv) < 3 or kv[2] == 1 or self.head_dim != 128:
             return False
         if getattr(self.o, "_gf_w8", None) is not None:
             return False
@@ -530,6 +579,13 @@ class DiTBlock(nn.Module):
         self.modulation = nn.Parameter(torch.randn(1, 6, dim) / dim ** 0.5)
         self.gate = GateModule()
 
+    def _normed(self, x2, fp8: bool, out, **kw):
+        """LayerNorm(+affine)(+modulate) of x2 as the input of the linears that follow: under fp8 the normalised row goes straight
+        to e4m3 + scale_a (never to HBM as bf16), else into the bf16 buffer `out` (None: a new one) — which is returned."""
+        if fp8:
+            return QuantizedInput.layernorm(x2, eps=self.eps, **kw)
+        return ops.layernorm_modulate(x2, eps=self.eps, out=out, **kw)
+
     def forward(self, x, context, t_mod, freqs, context_kv=None, out=None, sp=None, keep=None, self_attn_memo=None,
                 fold_pad_keys=True, pad_n=None, dense_attn=False):
         """`dense_attn`: SelfAttention.attend's `dense` (a sparse-switched block attends densely in this call).
@@ -555,10 +611,7 @@ class DiTBlock(nn.Module):
                 x_new = out.copy_(x_new)
             h = None if fp8 else torch.empty_like(x2)
         else:
-            if fp8:                              # the normalised row goes straight to e4m3 + scale_a (never to HBM as bf16)
-                h = QuantizedInput.layernorm(x2, scale1p=mod[1], shift=mod[0], eps=self.eps)
-            else:
-                h = ops.layernorm_modulate(x2, scale1p=mod[1], shift=mod[0], eps=self.eps)          # DIT:225
+            h = self._normed(x2, fp8, None, scale1p=mod[1], shift=mod[0])                              # DIT:225
             a = self.self_attn.attend(h, rope, sp, keep, dense=dense_attn)
             x_new = out if out is not None else torch.empty_like(x2)
             linear(a, self.self_attn.o, epilogue=ops.EPI_BIAS_GATE_RESID, resid=x2, gate=mod[2], out=x_new)   # DIT:226
@@ -569,10 +622,7 @@ class DiTBlock(nn.Module):
                 if x_new.is_cuda:
                     self_attn_memo["ev"] = torch.cuda.Event()
                     self_attn_memo["ev"].record(torch.cuda.current_stream(x_new.device))
-        if fp8:
-            h = QuantizedInput.layernorm(x_new, weight=self.norm3.weight, bias=self.norm3.bias, eps=self.eps)
-        else:
-            ops.layernorm_modulate(x_new, weight=self.norm3.weight, bias=self.norm3.bias, eps=self.eps, out=h)
+        h = self._normed(x_new, fp8, h, weight=self.norm3.weight, bias=self.norm3.bias)
         if context_kv is None:
             context_kv = self.cross_attn.context_kv(_tokens2d(context), fold=fold_pad_keys and keep is None, pad_n=pad_n)
         ca = self.cross_attn
@@ -585,10 +635,7 @@ class DiTBlock(nn.Module):
             linear(a, ca.o, epilogue=ops.EPI_BIAS_RESID, resid=x_new, out=x_new)                        # DIT:227
         if keep is not None and keep.get("wide"):
             keep["x2b"] = x_new.clone()
-        if fp8:
-            h = QuantizedInput.layernorm(x_new, scale1p=mod[4], shift=mod[3], eps=self.eps)
-        else:
-            ops.layernorm_modulate(x_new, scale1p=mod[4], shift=mod[3], eps=self.eps, out=h)     # DIT:228
+        h = self._normed(x_new, fp8, h, scale1p=mod[4], shift=mod[3])                                  # DIT:228
         f1 = linear(h, self.ffn[0], epilogue=ops.EPI_BIAS_GELU_TANH)
         linear(f1, self.ffn[2], epilogue=ops.EPI_BIAS_GATE_RESID, resid=x_new, gate=mod[5], out=x_new)  # DIT:229
         return x_new.view(x.shape)

@@ -128,7 +128,7 @@ def model_fn_wan_video(
     else:
         ctx = dit.embed_text(context)
         # ONE read-back per embedded context; the blocks below take n instead of detecting the run again
-        pad_n = pad_run(ctx[0]) if ops._OPT["fold_pad_keys"] else None
+        pad_n = pad_run(ctx[0]) if ops.option("fold_pad_keys") else None
         if context_cache is not None:
             context_cache.ctx, context_cache.pad_n = ctx, pad_n
 

@@ -296,6 +296,11 @@ _OPT = {"attn_k3": True, "vt_from_gemm": True, "conv_padded": True, "fold_pad_ke
         "fold_cross_o": True}
 
 
+def option(name: str) -> bool:
+    """The value of a module-side dispatch option (`_OPT`, above) as `ops.options` last set it."""
+    return _OPT[name]
+
+
 def lib_option(name: str) -> int:
     """The value of a library-side dispatch option as the LIBRARY holds it (gf_get_option) — not a Python mirror: a caller that
     used gf_set_option / gf_reset_options directly is seen."""

@@ -171,10 +171,3 @@ class SequenceParallel:
         if not torch.equal(recv[:, 0].float(), want):
             raise GoalForceError("sequence-parallel pre-flight: the head all-to-all delivered the wrong blocks")
         return t.numel() * 2 * (p - 1) // p
-
-
-def attention(sp: Optional[SequenceParallel], q, k, v, num_heads: int):
-    """Self-attention entry of the DiT blocks: plain flash-attention without a group, Ulysses with one."""
-    if sp is None:
-        return ops.flash_attn(q, k, v, num_heads)
-    return sp.attention(q, k, v, num_heads)

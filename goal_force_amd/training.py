@@ -29,7 +29,7 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import GoalForceError
-from .dit import Q_PRESCALE, DiTBlock, RopeTable, WanModel, _tokens2d
+from .dit import DiTBlock, RopeTable, WanModel, _tokens2d, q_rotation, refuse_training
 
 BF = torch.bfloat16
 
@@ -252,19 +252,9 @@ class DiTBlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, block, rope, x2, ctx2, t_mod, *params):
         ctx.block, ctx.rope = block, rope
-        if any(getattr(m, "_gf_w8", None) is not None for m in block.modules()):
-            # the backward recomputes the block on the bf16 kernels: an fp8 forward would not be the function differentiated
-            raise GoalForceError("training through an enable_fp8 block is refused: call enable_fp8(module, False) first")
-        if getattr(block.self_attn, "_gf_sage", False):
-            # no backward exists for the sage backend (nor in the sageattention package): the backward would differentiate another function
-            raise GoalForceError("training through a block with enable_sage_attention is refused: call enable_sage_attention(module, False) first")
-        if getattr(block.self_attn, "_gf_sparse", None) is not None:
-            # there is no sparse backward: the backward recomputes and differentiates the DENSE attention, whatever the keep level
-            # (with keep level "none" the forward's own refusal, SelfAttention.attend(keep=...), is never reached)
-            raise GoalForceError("training through a block with enable_sparse_attention is refused (there is no sparse backward): "
-                                 "call enable_sparse_attention(module, None) first")
+        refuse_training(block)
         ctx.param_needs = [p.requires_grad for p in params]
-        ctx.q_prescale = bool(ops._OPT["attn_q_prescale"])       # what the forward's self-attention saw is what the backward rebuilds (dit.SelfAttention.attend)
+        ctx.q_prescale = bool(ops.option("attn_q_prescale"))       # what the forward's self-attention saw is what the backward rebuilds (dit.q_rotation)
         keep = ({"wide": True} if _wide_fits(x2) else {}) if KEEP_ATTENTION else None
         with torch.no_grad():
             out = block(x2, ctx2, t_mod, rope, keep=keep, fold_pad_keys=False)   # the backward differentiates the unfolded graph
@@ -316,9 +306,7 @@ class DiTBlockFn(torch.autograd.Function):
         else:
             qp, kp, vv = lin(h1, sa.q), lin(h1, sa.k), lin(h1, sa.v)
         qn, kn = qp.clone(), kp.clone()
-        # the self-attention's q as the forward made it: pre-scaled through its rotation table, scale = ln 2 in the kernels (one
-        # rounding of q, and the SAME scores in the forward's log-sum-exp and in the backward's P)
-        (q_cos, q_sin), sa_scale = ((rope.scaled(Q_PRESCALE(hd)), math.log(2.0)) if ctx.q_prescale else ((rope.cos, rope.sin), None))
+        q_cos, q_sin, sa_scale = q_rotation(rope, hd, ctx.q_prescale)      # the self-attention's q as the forward made it: the SAME scores
         ops.rmsnorm_rope(qn, sa.norm_q.weight, q_cos, q_sin, hd, sa.norm_q.eps)
         ops.rmsnorm_rope(kn, sa.norm_k.weight, rope.cos, rope.sin, hd, sa.norm_k.eps)
         a, lse = kept if len(kept) else ops.flash_attn_lse(qn, kn, vv, heads, scale=sa_scale)

@@ -221,7 +221,7 @@ def frame_attention(qkv, C, out):
     kp = _pad_to(hw, 64)
     q, k, v = qkv[:, :, :C], qkv[:, :, C:2 * C], qkv[:, :, 2 * C:]
     scores = ops.gemm_batched(q, k)                                                # q k^T  [g, hw, hw]
-    if ops._OPT["vae_attn_offset"]:
+    if ops.option("vae_attn_offset"):
         qa = torch.zeros((g, hw, C + 64), dtype=qkv.dtype, device=qkv.device)      # [q, -rowmax, 0 ...]
         ka = torch.zeros((g, hw, C + 64), dtype=qkv.dtype, device=qkv.device)      # [k,    1,    0 ...]
         qa[:, :, :C].copy_(q)
@@ -401,7 +401,7 @@ class WanVideoVAE(nn.Module):
         """ResidualBlock (VAE:267-301)."""
         h = x if cin == cout else self._causal_conv(P, name + ".shortcut", x)
         # per convolution: the padded-layout kernel where the INPUT has 192 / 384 channels (conv 1: cin, conv 2: cout)
-        pad_ok = ops._OPT["conv_padded"] and x.is_contiguous()
+        pad_ok = ops.option("conv_padded") and x.is_contiguous()
         if pad_ok and ops.padded_conv_fits(*x.shape[:3], cin):
             y = self._padded_conv(P, name + ".residual.2", x, P[name + ".residual.0.gamma"])
         else:
@@ -456,7 +456,7 @@ class WanVideoVAE(nn.Module):
                 x = out
                 T = n0 + 2 * Tr
         rc = P[name + ".resample.1"]
-        if ops._OPT["conv_padded"] and rc["w"].shape[0] >= 192 and x.is_contiguous() \
+        if ops.option("conv_padded") and rc["w"].shape[0] >= 192 and x.is_contiguous() \
                 and ops.padded_conv_fits(T, 2 * H, 2 * W, C, history=False):
             # 384 -> 192: the upsampled frames go into the zero-bordered layout once (4 x the source, one pass) and the 3x3
             # convolution reads its taps as row shifts (gf_conv3d_padded_bf16, kt = 1) — same values, same sums as the folded gather
