@@ -184,10 +184,27 @@ def fp8_weight(lin: nn.Linear):
     return w8
 
 
+def fp4_weight(lin: nn.Linear):
+    """The layer's current MXFP4 weight copy (enable_fp4) as (packed e2m1 codes, E8M0 scales), or None."""
+    w4 = getattr(lin, "_gf_w4", None)
+    if w4 is not None and lin._gf_w4_key != param_key(lin.weight):          # the bf16 master changed since the quantisation: refresh the copy
+        w4 = lin._gf_w4 = ops.quant_mxfp4(lin.weight.detach().contiguous())
+        lin._gf_w4_key = param_key(lin.weight)
+    return w4
+
+
 def linear(x2, lin: nn.Linear, epilogue=ops.EPI_BIAS, resid=None, gate=None, out=None):
     """One nn.Linear on the MFMA GEMM.  If the layer carries an fp8 weight copy (enable_fp8) the reference's
     fp8_linear contract is used (VRAM:115-151: per-row dynamic activation scale, unit weight scale, e4m3),
-    otherwise the bf16 kernel.  x2 may be a QuantizedInput to reuse one quantisation for several layers."""
+    otherwise the bf16 kernel.  x2 may be a QuantizedInput to reuse one quantisation for several layers.
+    An MXFP4 weight copy (enable_fp4) wins over both: the bf16 input is quantised by ops.quant_mxfp4 and the product runs on
+    ops.gemm_mxfp4; a QuantizedInput (fp8) is refused there."""
+    w4 = fp4_weight(lin)
+    if w4 is not None:
+        if isinstance(x2, QuantizedInput):
+            raise GoalForceError("linear: an fp8 QuantizedInput was handed to an enable_fp4 layer, which quantises its own bf16 input")
+        x4, xs = ops.quant_mxfp4(x2)
+        return ops.gemm_mxfp4(x4, xs, w4[0], w4[1], lin.bias, epilogue=epilogue, resid=resid, gate=gate, out=out)
     w8 = fp8_weight(lin)
     if w8 is None:
         return ops.gemm(x2, lin.weight, lin.bias, epilogue=epilogue, resid=resid, gate=gate, out=out)
@@ -205,6 +222,38 @@ def enable_fp8(module: nn.Module, enabled=True):
                 if isinstance(lin, nn.Linear):
                     lin._gf_w8 = ops.cast_fp8(lin.weight.detach().contiguous()) if enabled else None
                     lin._gf_w8_key = param_key(lin.weight) if enabled else None
+    return module
+
+
+FP4_LAYERS = ("ffn", "o")
+
+
+def fp4_linears(blk: "DiTBlock", layers=FP4_LAYERS):
+    """The Linears of a block that the layer names of enable_fp4 stand for."""
+    named = {"ffn": (blk.ffn[0], blk.ffn[2]), "o": (blk.self_attn.o, blk.cross_attn.o)}
+    return [lin for name in layers for lin in named[name]]
+
+
+def enable_fp4(module: nn.Module, enabled=True, layers=FP4_LAYERS):
+    """MXFP4 linears (include/goalforce.h; the reference has no counterpart, off by default): the named Linears of every DiTBlock
+    inside `module` (a block, a WanModel, a ControlNet or a whole pipeline) get an MXFP4 weight copy (ops.quant_mxfp4: e2m1 codes,
+    one E8M0 scale per 32 input features) beside the bf16 master, and dit.linear runs them on ops.gemm_mxfp4 with the activation
+    quantised the same way per call.  "ffn" = ffn[0] and ffn[2], "o" = self_attn.o and cross_attn.o; q / k / v and the
+    cross-attention's k / v keep their fused bf16 / fp8 paths and any other name is refused.  An fp4 copy wins over an fp8 copy of
+    the same layer (enable_fp8); enabled=False removes the fp4 copies of the named layers and leaves whatever else was there.
+    A mechanism: the quality of a trained model under it has not been measured."""
+    layers = (layers,) if isinstance(layers, str) else tuple(layers)
+    bad = [name for name in layers if name not in FP4_LAYERS]
+    if bad:
+        raise GoalForceError(f"enable_fp4: unknown layer name {bad[0]!r}: expected a subset of {FP4_LAYERS} "
+                             "(q / k / v keep their fused bf16 / fp8 paths)")
+    for blk in module.modules():
+        if isinstance(blk, DiTBlock):
+            for lin in fp4_linears(blk, layers):
+                if enabled and lin.weight.shape[1] % 256:
+                    raise GoalForceError(f"enable_fp4: a Linear with {lin.weight.shape[1]} input features: gf_gemm_mxfp4 needs a multiple of 256")
+                lin._gf_w4 = ops.quant_mxfp4(lin.weight.detach().contiguous()) if enabled else None
+                lin._gf_w4_key = param_key(lin.weight) if enabled else None
     return module
 
 
@@ -251,6 +300,9 @@ def refuse_training(block: "DiTBlock"):
     if any(getattr(m, "_gf_w8", None) is not None for m in block.modules()):
         # the backward recomputes the block on the bf16 kernels: an fp8 forward would not be the function differentiated
         raise GoalForceError("training through an enable_fp8 block is refused: call enable_fp8(module, False) first")
+    if any(getattr(m, "_gf_w4", None) is not None for m in block.modules()):
+        # the same reason: the backward differentiates the bf16 block
+        raise GoalForceError("training through an enable_fp4 block is refused: call enable_fp4(module, False) first")
     if getattr(block.self_attn, "_gf_sage", False):
         # no backward exists for the sage backend (nor in the sageattention package): the backward would differentiate another function
         raise GoalForceError("training through a block with enable_sage_attention is refused: call enable_sage_attention(module, False) first")
@@ -520,7 +572,7 @@ class CrossAttention(nn.Module):
         2-head test models), ops.options(fold_cross_o) on."""
         if not ops.option("fold_cross_o") or torch.is_grad_enabled() or len(kv) < 3 or kv[2] == 1 or self.head_dim != 128:
             return False
-        if getattr(self.o, "_gf_w8", None) is not None:
+        if getattr(self.o, "_gf_w8", None) is not None or getattr(self.o, "_gf_w4", None) is not None:
             return False
         n = kv[0].shape[0]
         k = self.num_heads * self.fold_pad(n)          # the projection GEMM's K: a multiple of 64 (gf_gemm_bf16)
@@ -599,8 +651,10 @@ class DiTBlock(nn.Module):
         rope = _as_rope(freqs, x.device)
         # rows: shift_msa, 1+scale_msa, gate_msa, shift_mlp, 1+scale_mlp, gate_mlp   (DIT:218-219, 64-65)
         mod = ops.modulation(self.modulation, t_mod.contiguous(), onep_mask=0b010010)
-        # config 5: every Linear of the block on the fp8_linear contract — all of them or none (enable_fp8)
-        fp8 = getattr(self.ffn[0], "_gf_w8", None) is not None
+        # config 5: every Linear of the block on the fp8_linear contract — all of them or none (enable_fp8).  Read from a layer
+        # enable_fp4 never takes; an fp4 layer wants its input in bf16 whatever this flag says
+        fp8 = getattr(self.self_attn.q, "_gf_w8", None) is not None
+        fp4_ffn = getattr(self.ffn[0], "_gf_w4", None) is not None
         if self_attn_memo is not None and "x" in self_attn_memo:
             x_new = self_attn_memo.pop("x")
             ev = self_attn_memo.pop("ev", None)
@@ -635,7 +689,7 @@ class DiTBlock(nn.Module):
             linear(a, ca.o, epilogue=ops.EPI_BIAS_RESID, resid=x_new, out=x_new)                        # DIT:227
         if keep is not None and keep.get("wide"):
             keep["x2b"] = x_new.clone()
-        h = self._normed(x_new, fp8, h, scale1p=mod[4], shift=mod[3])                                  # DIT:228
+        h = self._normed(x_new, fp8 and not fp4_ffn, None if fp8 else h, scale1p=mod[4], shift=mod[3])  # DIT:228
         f1 = linear(h, self.ffn[0], epilogue=ops.EPI_BIAS_GELU_TANH)
         linear(f1, self.ffn[2], epilogue=ops.EPI_BIAS_GATE_RESID, resid=x_new, gate=mod[5], out=x_new)  # DIT:229
         return x_new.view(x.shape)

@@ -1508,6 +1508,57 @@ def gemm_fp8(a8, row_scale, w8, bias=None, epilogue=EPI_BIAS, resid=None, gate=N
     return _gemm(a8, w8, row_scale, bias, epilogue, resid, gate, out)
 
 
+# ---------------------------------------------------------------------------------- MXFP4 Linear (goalforce.h; no reference counterpart)
+
+
+def quant_mxfp4(x):
+    """x [M,K] bf16 (rows may be strided) -> (x4 [M,K/2] uint8 packed e2m1, scale [M,K/32] uint8 E8M0) — gf_quant_mxfp4; K % 32 == 0."""
+    _req(x, "quant_mxfp4.x")
+    xv, rows, dim, xs = _rows2d(x, "quant_mxfp4.x")
+    if dim % 32:
+        raise GoalForceError(f"quant_mxfp4.x: the row length {dim} must be a multiple of 32 (one E8M0 scale per 32 elements)")
+    out = torch.empty((rows, dim // 2), dtype=torch.uint8, device=x.device)
+    scale = torch.empty((rows, dim // 32), dtype=torch.uint8, device=x.device)
+    _lib.check(_lib.load().gf_quant_mxfp4(_ptr(xv), xs, _ptr(out), dim // 2, _ptr(scale), dim // 32, rows, dim, _stream(x)),
+               "gf_quant_mxfp4")
+    return out, scale
+
+
+def gemm_mxfp4(a4, a_scale, w4, w_scale, bias=None, epilogue=EPI_BIAS, resid=None, gate=None, out=None):
+    """out[M,N] = epilogue(bf16(deq(a4, a_scale) @ deq(w4, w_scale)^T + bias)) — gf_gemm_mxfp4.  a4 [M,K/2] / w4 [N,K/2] uint8 packed
+    e2m1, a_scale [M,K/32] / w_scale [N,K/32] uint8 E8M0 (ops.quant_mxfp4); K % 256 == 0.  The checks and their words are _gemm's."""
+    _mat(a4, "mxfp4 linear: activation", torch.uint8)
+    M, K2 = a4.shape
+    K = 2 * K2
+    N, ldw = _weight(w4, "mxfp4 linear: weight", K2, torch.uint8)
+    for t, name, rows in ((a_scale, "mxfp4 linear: activation scales", M), (w_scale, "mxfp4 linear: weight scales", N)):
+        if t is None:
+            raise GoalForceError(f"{name}: required")
+        _mat(t, name, torch.uint8)
+        if tuple(t.shape) != (rows, K // 32):
+            raise GoalForceError(f"{name}: expected [{rows}, {K // 32}], got {tuple(t.shape)}")
+    if out is None:
+        out = torch.empty((M, N), dtype=_BF16, device=a4.device)
+    ov, Mo, No, ldc = _rows2d(out, "gemm_mxfp4.out")
+    if (Mo, No) != (M, N):
+        raise GoalForceError(f"gemm_mxfp4.out: expected [{M}, {N}], got [{Mo}, {No}]")
+    ldr = 0
+    if resid is not None:
+        _req(resid, "gemm_mxfp4.resid")
+        resid, Mr, Nr, ldr = _rows2d(resid, "gemm_mxfp4.resid")
+        if (Mr, Nr) != (M, N):
+            raise GoalForceError(f"gemm_mxfp4.resid: expected [{M}, {N}], got [{Mr}, {Nr}]")
+    _vec(gate, "gemm_mxfp4.gate", N)
+    _vec(bias, "gemm_mxfp4.bias", N)
+    if M == 0:                       # nothing to compute (an empty tensor has no address to hand over)
+        return out
+    with _timed(PROFILE_GEMM, M, N, K, int(epilogue)):
+        _lib.check(_lib.load().gf_gemm_mxfp4(_ptr(a4), a4.stride(0), _ptr(a_scale), a_scale.stride(0), _ptr(w4), ldw, _ptr(w_scale),
+                                             w_scale.stride(0), _ptr(bias), _ptr(ov), ldc, M, N, K, int(epilogue), _ptr(resid), ldr,
+                                             _ptr(gate), _stream(a4)), "gf_gemm_mxfp4")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # backward / training ops (gf_backward.hip, gf_attention_bwd.hip)
 def _f32(t, name):

@@ -615,6 +615,42 @@ GF_API int gf_gemm_fp8(const void* A8, int64_t lda, const void* W8, int64_t ldw,
                        const void* bias, void* C, int64_t ldc, int64_t M, int64_t N, int64_t K,
                        int epilogue, const void* resid, int64_t ldr, const void* gate, void* stream);
 
+/* ========================================================================
+ * MXFP4 Linear — OCP Microscaling FP4 (no counterpart in the reference; off by default, dit.enable_fp4).  The format, stated once:
+ *   element  e2m1, code s|ee|m: magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6 (codes 0..7), bit 3 the sign
+ *   packing  byte i of a row holds element 2i in bits 3:0 and element 2i+1 in bits 7:4
+ *   scale    one E8M0 byte per 32 consecutive k: value 2^(code - 127), code 255 = NaN; stored row-major [rows, K/32] with a stride
+ * Quantiser recipe (bf16 in, blocks of 32 along the contiguous dimension; every step exact arithmetic on power-of-two scalings):
+ *   amax = the largest |x| of the block (exact: bf16 subnormals are not flushed);  amax = 0 -> code 127, all elements +0
+ *   else e = floor(log2 amax) - 2, code = clamp(e + 127, 0, 254)  (bf16's exponent range reaches codes 0 .. 252 only)
+ *   element = x * 2^-(code - 127) rounded to the nearest e2m1 value, ties to the even mantissa code (5 -> 4, 2.5 -> 2, 0.25 -> 0),
+ *   the magnitude saturating at 6 (7 -> 6), the sign kept (-0 and values that round to zero keep their sign bit)
+ *   a block holding any NaN or +-inf -> code 255, all elements +0
+ * ======================================================================== */
+
+/* gf_quant_mxfp4 — x [rows, dim] bf16 (row stride x_stride elements) -> out4 [rows, dim/2] packed bytes (row stride out_stride bytes)
+ * and scales [rows, dim/32] E8M0 bytes (row stride scale_stride bytes), one pass; serves activations and weights alike.
+ * dim % 32 == 0; x 16-byte aligned with x_stride % 8 == 0; out4 4-byte aligned with out_stride % 4 == 0; rows = 0 is a no-op. */
+GF_API int gf_quant_mxfp4(const void* x, int64_t x_stride, void* out4, int64_t out_stride, void* scales, int64_t scale_stride,
+                          int64_t rows, int64_t dim, void* stream);
+
+/* gf_gemm_mxfp4 — C = epilogue(bf16(sum_k A^[m,k] W^[n,k] + bias)), A^ / W^ the dequantised operands: A4 [M, K/2] / W4 [N, K/2] packed
+ * e2m1 (lda / ldw in BYTES, multiples of 16), a_scale [M, K/32] / w_scale [N, K/32] E8M0 with their row strides in bytes.  The block
+ * scales are applied inside v_mfma_scale_f32_16x16x128_f8f6f4 (both operands e2m1: 4x the bf16 MFMA rate); no row scale in the
+ * epilogue.  Epilogues, bf16 rounding sequence, residual / gate semantics and C-aliases-resid are gf_gemm_bf16's.
+ * Any M >= 0, N % 8 == 0, K % 256 == 0 (one 128-byte LDS row = 256 elements = two MFMA k-steps).
+ * NaN: a row of A whose scale row holds code 255 comes out NaN in all its columns, a row of W with one makes its column NaN.
+ * OBSERVED on an MI355X (one instruction per wave, no vendor statement): the instruction itself returns NaN for every output of a lane's
+ * row / column whose scale byte is 255, also over a block of zeros and whatever the other operand holds.  The kernel does not rely on
+ * it: its epilogue sets those rows / columns to NaN from the scale bytes it fetched.
+ * Accumulation, as measured (tests/fp4_refs.py::MODEL_NOTE): products inside a block are summed exactly; with the four
+ * blocks' scale sums within 2^+-4 and a zero accumulator the result is the exact sum rounded to fp32; beyond that it is a fixed-point
+ * adder — a block 22 - 23 binades below the instruction's largest scale sum is dropped, bits about 23 below it are cut — so an output
+ * is within K 2^-23 S + T of the exact product (T: fp4_refs.mfma_mxfp4; about one fp32 ulp of S on operands from gf_quant_mxfp4). */
+GF_API int gf_gemm_mxfp4(const void* A4, int64_t lda, const void* a_scale, int64_t a_scale_stride, const void* W4, int64_t ldw,
+                         const void* w_scale, int64_t w_scale_stride, const void* bias, void* C, int64_t ldc, int64_t M, int64_t N,
+                         int64_t K, int epilogue, const void* resid, int64_t ldr, const void* gate, void* stream);
+
 /* ------------------------------------------------------------------------
  * gf_conv3d_padded_bf16 — CausalConv3d 3x3x3, stride 1 (VAE:33-52) of the 192- and 384-channel levels of Decoder3d / Encoder3d
  * (VAE:736-838, 517-617) as a direct convolution on the 4-wave GEMM loop (gf_conv_a4.hip).
