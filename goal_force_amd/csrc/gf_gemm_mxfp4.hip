@@ -1,6 +1,7 @@
 // gf_gemm_mxfp4.hip — OCP MXFP4 linears (include/goalforce.h, "MXFP4 Linear"): the quantiser gf_quant_mxfp4 (bf16 -> packed e2m1
 // codes + one E8M0 scale per 32 k) and the block-scaled GEMM gf_gemm_mxfp4 on v_mfma_scale_f32_16x16x128_f8f6f4 with both operands
-// e2m1 (cbsz = blgp = 4) and the blocks' scales in the instruction's scale operands.
+// e2m1 (cbsz = blgp = 4) and the blocks' scales in the instruction's scale operands; gf_gemm_mxfp4_q4 is that GEMM with its output
+// quantised in the epilogue, for a consumer that is another fp4 Linear.
 //
 // The GEMM is the 8-wave one-barrier kernel of the fp8 small shapes (gf_gemm.hip, gemm_kernel<EPI, true>) with another element:
 //   * 256x256 output tile per 512-thread workgroup (8 waves as 2(M) x 4(N), 128x64 per wave), fp32 accumulators;
@@ -19,6 +20,7 @@
 // through v_mov and spilled 29 - 63 VGPRs, and every reload waited (vmcnt) for the next tile's DMA as well: 0.77 -> 0.51 ms at
 // 32760 x 5120 x 5120 once it was gone (197 VGPRs, no scratch).
 #include "gf_mfma_frame.h"
+#include "gf_mxfp4_quant.h"
 
 namespace {
 
@@ -44,6 +46,10 @@ struct Fp4Args {
     int M, N, K;
     long lda, ldw, lsa, lsw, ldc, ldr;
     int tiles_m, tiles_n;
+    // Q4 (gf_gemm_mxfp4_q4): the output as the next GEMM's A operand instead of C — packed codes [M, N/2] and scales [M, N/32], strides in bytes
+    unsigned char* C4;
+    unsigned char* sc;
+    long ldc4, lsc;
 };
 
 // the Linear's own output is rounded to bf16 before an activation is applied to it: the expression of gf_gemm.hip's epilogues
@@ -56,7 +62,10 @@ __device__ __forceinline__ float fp4_epi_act(float lin) {
     } else return lin;
 }
 
-template <int EPI>
+// Q4: the finished bf16 output is quantised to MXFP4 in the read-back loop (gf_mxfp4_quant.h) and only its codes and scales are stored:
+// a lane of that loop holds 8 consecutive columns of one row and lanes cc = 0..3 / 4..7 are the two 32-aligned MX blocks of the wave's
+// 64 columns — the quantiser's own arrangement.  Epilogues without a second operand only.
+template <int EPI, bool Q4 = false>
 __global__ __launch_bounds__(FP4_THREADS, 2) void gemm_mxfp4_kernel(const Fp4Args p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     GF_LDS char* lds = (GF_LDS char*)smem;
@@ -242,7 +251,14 @@ __global__ __launch_bounds__(FP4_THREADS, 2) void gemm_mxfp4_kernel(const Fp4Arg
             const int row = it * 8 + rr;
             const int m = m0 + wm * 128 + row;
             const u16x8 yv = *(GF_LDS u16x8*)(ep + row * 128 + ((cc ^ (row & 7)) << 4));
-            if (m < p.M && n_ok) {
+            if constexpr (Q4) {
+                int code;       // the block step shuffles: in front of the tail branch; N % 32 == 0, so a block's four lanes share n_ok
+                const unsigned packed = mxfp4_block_step(yv, code);
+                if (m < p.M && n_ok) {
+                    *reinterpret_cast<unsigned*>(p.C4 + (long)m * p.ldc4 + (n >> 1)) = packed;
+                    if ((cc & 3) == 0) p.sc[(long)m * p.lsc + (n >> 5)] = (unsigned char)code;
+                }
+            } else if (m < p.M && n_ok) {
                 u16x8 o = yv;
                 if (EPI == GF_EPI_BIAS_GATE_RESID || EPI == GF_EPI_BIAS_RESID || EPI == GF_EPI_BIAS_MUL) {
                     const u16x8 r8 = *reinterpret_cast<const u16x8*>(p.R + (long)m * p.ldr + n);
@@ -261,23 +277,7 @@ __global__ __launch_bounds__(FP4_THREADS, 2) void gemm_mxfp4_kernel(const Fp4Arg
 }
 
 // ---- the quantiser: thread = 8 consecutive elements (one 16-byte load), four neighbouring lanes = one MX block ---------------------
-// Everything is integer work on the bf16 bit patterns and exact power-of-two scalings: no step depends on the denormal mode.
-__device__ __forceinline__ unsigned e2m1_code(unsigned bits, int code) {
-    // |x| = sig * 2^ex (bf16: normal sig = 128 + mantissa, ex = exponent field - 134; subnormal sig = mantissa, ex = -133)
-    const unsigned a = bits & 0x7FFFu;
-    const int ef = (int)(a >> 7);
-    const int sig = ef ? (int)(128u | (a & 127u)) : (int)(a & 127u);
-    // v = |x| * 2^-(code - 127) = sig * 2^t, below 8 by the choice of the code; far below 1/4 (t < -40) it rounds to 0 like anything there
-    const int t = max((ef ? ef : 1) - 134 - code + 127, -40);
-    const float v = sig ? __uint_as_float(__float_as_uint((float)sig) + ((unsigned)t << 23)) : 0.0f;   // a normal fp32, exact
-    // e2m1's grid: steps of 1/2 below 2, of 1 below 4, of 2 above; v_rndne rounds ties to the even multiple = the even mantissa code
-    int c;
-    if (v < 2.0f) c = (int)__builtin_rintf(v * 2.0f);                 // 0, .5, 1, 1.5, (2)   -> codes 0..4
-    else if (v < 4.0f) c = 2 + (int)__builtin_rintf(v);               // 2, 3, (4)            -> codes 4..6
-    else c = min(4 + (int)__builtin_rintf(v * 0.5f), 7);              // 4, 6, saturating     -> codes 6, 7
-    return (unsigned)c | ((bits >> 12) & 8u);
-}
-
+// The block step itself is gf_mxfp4_quant.h's, shared with the two producers that quantise in registers.
 __global__ __launch_bounds__(256) void quant_mxfp4_kernel(const u16* __restrict__ x, long x_stride, unsigned char* __restrict__ out4,
                                                           long out_stride, unsigned char* __restrict__ scales, long scale_stride,
                                                           long total, int cpr) {
@@ -287,23 +287,8 @@ __global__ __launch_bounds__(256) void quant_mxfp4_kernel(const u16* __restrict_
     const long row = g / cpr;
     const int c = (int)(g - row * cpr);
     const u16x8 xv = *reinterpret_cast<const u16x8*>(x + row * x_stride + (long)c * 8);
-    unsigned amax = 0;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) amax = max(amax, (unsigned)(xv[e] & 0x7FFFu));   // |x| orders like its bits; NaN / inf are >= 0x7F80
-    amax = max(amax, (unsigned)__shfl_xor((int)amax, 1));
-    amax = max(amax, (unsigned)__shfl_xor((int)amax, 2));
     int code;
-    unsigned packed = 0;
-    if (amax >= 0x7F80u) code = 255;                                  // a NaN or an infinity in the block: NaN scale, elements +0
-    else if (amax == 0) code = 127;
-    else {
-        const int ef = (int)(amax >> 7);
-        // floor(log2 amax): exponent field - 127, subnormals by their leading mantissa bit; code = that - 2 + 127, clamped to 0 .. 254
-        const int fl = ef ? ef - 127 : -133 + (31 - __builtin_clz(amax & 127u));
-        code = min(max(fl - 2 + 127, 0), 254);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) packed |= e2m1_code(xv[e], code) << (4 * e);   // element 2i in bits 3:0 of byte i, 2i+1 in bits 7:4
-    }
+    const unsigned packed = mxfp4_block_step(xv, code);      // every lane: a dead one re-does the last piece
     if (live) {
         *reinterpret_cast<unsigned*>(out4 + row * out_stride + (long)c * 4) = packed;
         if ((c & 3) == 0) scales[row * scale_stride + (c >> 2)] = (unsigned char)code;
@@ -314,6 +299,12 @@ template <int EPI>
 int launch_mxfp4(const Fp4Args& a, hipStream_t stream) {
     return gf_launch_lds<gemm_mxfp4_kernel<EPI>>("gf_gemm_mxfp4", GF_ATTR_MSG_BYTES, "gf_gemm_mxfp4", dim3((unsigned)(a.tiles_m * a.tiles_n)),
                                                   dim3(FP4_THREADS), FP4_LDS, stream, a);
+}
+
+template <int EPI>
+int launch_mxfp4_q4(const Fp4Args& a, hipStream_t stream) {
+    return gf_launch_lds<gemm_mxfp4_kernel<EPI, true>>("gf_gemm_mxfp4_q4", GF_ATTR_MSG_BYTES, "gf_gemm_mxfp4_q4",
+                                                        dim3((unsigned)(a.tiles_m * a.tiles_n)), dim3(FP4_THREADS), FP4_LDS, stream, a);
 }
 
 }  // namespace
@@ -377,6 +368,8 @@ extern "C" GF_API int gf_gemm_mxfp4(const void* A4, int64_t lda, const void* a_s
     a.lsw = w_scale_stride;
     a.ldc = ldc;
     a.ldr = ldr;
+    a.C4 = a.sc = nullptr;
+    a.ldc4 = a.lsc = 0;
     a.tiles_m = (int)((M + BM - 1) / BM);
     a.tiles_n = (int)((N + BN - 1) / BN);
     hipStream_t s = (hipStream_t)stream;
@@ -387,5 +380,60 @@ extern "C" GF_API int gf_gemm_mxfp4(const void* A4, int64_t lda, const void* a_s
         case GF_EPI_BIAS_RESID: return launch_mxfp4<GF_EPI_BIAS_RESID>(a, s);
         case GF_EPI_BIAS_SILU: return launch_mxfp4<GF_EPI_BIAS_SILU>(a, s);
         default: return launch_mxfp4<GF_EPI_BIAS_MUL>(a, s);
+    }
+}
+
+extern "C" GF_API int gf_gemm_mxfp4_q4(const void* A4, int64_t lda, const void* a_scale, int64_t a_scale_stride, const void* W4, int64_t ldw,
+                                       const void* w_scale, int64_t w_scale_stride, const void* bias, void* C4, int64_t ldc4, void* c_scale,
+                                       int64_t c_scale_stride, int64_t M, int64_t N, int64_t K, int epilogue, void* stream) {
+    const char* fn = "gf_gemm_mxfp4_q4";
+    GF_CHECK_ARG(A4 && W4 && C4 && c_scale && a_scale && w_scale, "%s: null A/W/C/scales", fn);
+    GF_CHECK_ARG(M >= 0 && N > 0 && K > 0, "%s: bad sizes M=%ld N=%ld K=%ld", fn, (long)M, (long)N, (long)K);
+    GF_CHECK_ARG(K % 256 == 0, "%s: K=%ld must be a multiple of %d", fn, (long)K, 256);
+    GF_CHECK_ARG(N % 32 == 0, "%s: N=%ld must be a multiple of 32 (one E8M0 scale per 32 output columns)", fn, (long)N);
+    GF_CHECK_ARG(lda % 16 == 0 && ldw % 16 == 0 && ldc4 % 16 == 0 && lda >= K / 2 && ldw >= K / 2 && ldc4 >= N / 2,
+                 "%s: leading dimensions must be multiples of %d (A/W/C4, in bytes) and cover the row", fn, 16);
+    GF_CHECK_ARG(a_scale_stride >= K / 32 && w_scale_stride >= K / 32, "%s: scale strides must cover K/32 = %ld blocks", fn, (long)(K / 32));
+    GF_CHECK_ARG(c_scale_stride >= N / 32, "%s: c_scale_stride must cover N/32 = %ld blocks", fn, (long)(N / 32));
+    GF_CHECK_ARG(gf_aligned16(A4) && gf_aligned16(W4) && gf_aligned16(C4) && (!bias || gf_aligned16(bias)),
+                 "%s: 16-byte alignment required", fn);
+    GF_CHECK_ARG(M < (1 << 30) && N < (1 << 30), "%s: M/N too large", fn);
+    GF_CHECK_ARG(256L * lda + K / 2 < (1L << 31) && 256L * ldw + K / 2 < (1L << 31) && 256L * a_scale_stride + K / 32 < (1L << 31) &&
+                     256L * w_scale_stride + K / 32 < (1L << 31),
+                 "%s: operand too large for 32-bit staging offsets", fn);
+    GF_CHECK_ARG(epilogue >= GF_EPI_BIAS && epilogue <= GF_EPI_BIAS_MUL, "%s: unknown epilogue %d", fn, epilogue);
+    GF_CHECK_ARG(epilogue == GF_EPI_BIAS || epilogue == GF_EPI_BIAS_GELU_TANH || epilogue == GF_EPI_BIAS_SILU,
+                 "%s: epilogue %d takes a second operand; the quantising epilogue serves GF_EPI_BIAS, GF_EPI_BIAS_GELU_TANH and "
+                 "GF_EPI_BIAS_SILU (use gf_gemm_mxfp4 + gf_quant_mxfp4)", fn, epilogue);
+    if (M == 0) return GF_OK;
+    Fp4Args a;
+    a.A = (const char*)A4;
+    a.W = (const char*)W4;
+    a.sa = (const unsigned char*)a_scale;
+    a.sw = (const unsigned char*)w_scale;
+    a.bias = (const u16*)bias;
+    a.C = nullptr;
+    a.R = nullptr;
+    a.gate = nullptr;
+    a.M = (int)M;
+    a.N = (int)N;
+    a.K = (int)K;
+    a.lda = lda;
+    a.ldw = ldw;
+    a.lsa = a_scale_stride;
+    a.lsw = w_scale_stride;
+    a.ldc = 0;
+    a.ldr = 0;
+    a.tiles_m = (int)((M + BM - 1) / BM);
+    a.tiles_n = (int)((N + BN - 1) / BN);
+    a.C4 = (unsigned char*)C4;
+    a.sc = (unsigned char*)c_scale;
+    a.ldc4 = ldc4;
+    a.lsc = c_scale_stride;
+    hipStream_t s = (hipStream_t)stream;
+    switch (epilogue) {
+        case GF_EPI_BIAS: return launch_mxfp4_q4<GF_EPI_BIAS>(a, s);
+        case GF_EPI_BIAS_GELU_TANH: return launch_mxfp4_q4<GF_EPI_BIAS_GELU_TANH>(a, s);
+        default: return launch_mxfp4_q4<GF_EPI_BIAS_SILU>(a, s);
     }
 }

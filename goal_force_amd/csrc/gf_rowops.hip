@@ -9,6 +9,7 @@
 //   RMSNorm .float() norm, .to(bf16), * weight .. diffsynth/models/wan_video_dit.py:100-111
 //   rope_apply on adjacent pairs ................ diffsynth/models/wan_video_dit.py:92-97
 #include "gf_common.h"
+#include "gf_mxfp4_quant.h"
 
 namespace {
 
@@ -137,10 +138,13 @@ __global__ __launch_bounds__(ROW_THREADS) void rmsnorm_rope_kernel(
 // the 128-thread kernels above stay for every other width.
 constexpr int WROWS = 4;
 
-template <int NCH>
+// MX4: the row goes out as MXFP4 (gf_mxfp4_quant.h) — `out` is then the packed codes with out_stride in BYTES, `scales` / scale_stride
+// the E8M0 bytes; a lane's 8 columns are a quarter of an MX block and the block's scale is local to the chunk, so nothing is kept.
+template <int NCH, bool MX4 = false>
 __global__ __launch_bounds__(64 * WROWS) void layernorm_modulate_wave_kernel(
     const u16* __restrict__ x, u16* __restrict__ out, const u16* __restrict__ weight, const u16* __restrict__ bias,
-    const u16* __restrict__ scale1p, const u16* __restrict__ shift, long rows, long x_stride, long out_stride, float eps) {
+    const u16* __restrict__ scale1p, const u16* __restrict__ shift, long rows, long x_stride, long out_stride, float eps,
+    unsigned char* __restrict__ scales = nullptr, long scale_stride = 0) {
     constexpr int DIM = NCH * 512;
     const long row = (long)blockIdx.x * WROWS + (threadIdx.x >> 6);
     if (row >= rows) return;
@@ -164,7 +168,7 @@ __global__ __launch_bounds__(64 * WROWS) void layernorm_modulate_wave_kernel(
             q = __builtin_fmaf(d, d, q);   // written out: left to fp-contract, `q += d * d` may fuse the first two squares either way round
         }
     const float rstd = 1.0f / sqrtf(__builtin_fmaf(wave_sum(q), 1.0f / DIM, eps));
-    u16* orow = out + row * out_stride + lane * 8;
+    u16* orow = MX4 ? nullptr : out + row * out_stride + lane * 8;
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
         const int c0 = i * 512 + lane * 8;
@@ -183,7 +187,12 @@ __global__ __launch_bounds__(64 * WROWS) void layernorm_modulate_wave_kernel(
             if (shift) y = rbf(y + bf2f(sh8[j]));         // + shift
             o[j] = f2bf(y);
         }
-        *reinterpret_cast<u16x8*>(orow + i * 512) = o;
+        if constexpr (MX4) {   // the whole wave is here (row is wave-uniform): all four lanes of every block take the step's shuffles
+            int code;
+            const unsigned packed = mxfp4_block_step(o, code);
+            *reinterpret_cast<unsigned*>((unsigned char*)out + row * out_stride + (c0 >> 1)) = packed;
+            if ((lane & 3) == 0) scales[row * scale_stride + (c0 >> 5)] = (unsigned char)code;
+        } else *reinterpret_cast<u16x8*>(orow + i * 512) = o;
     }
 }
 
@@ -197,6 +206,9 @@ __global__ __launch_bounds__(64 * WROWS) void layernorm_modulate_wave_kernel(
 //   MODE 1: LayerNorm * a + b              (a = weight, b = bias: norm3)
 //   MODE 2: modulate(LayerNorm, b, a)      (a = 1 + scale, b = shift: norm1 / norm2 / head, the reference's three bf16 roundings)
 //   FP8: the result is quantised in registers for an fp8_linear consumer (layernorm_modulate_fp8_wave_kernel's contract).
+//   MX4: the result is quantised to MXFP4 in registers for an fp4 Linear (gf_mxfp4_quant.h): outp = the packed codes, out_stride in
+//        bytes, mx_scales / mx_stride the E8M0 bytes.  The scale is local to a 32-column block = four lanes of one chunk, so each chunk
+//        is quantised and stored inside the chunk loop.
 __device__ __forceinline__ gf_f32x2 unpack2bf(unsigned u) { return gf_f32x2{__uint_as_float(u << 16), __uint_as_float(u & 0xffff0000u)}; }
 // (contract off: a product must stay a product — the roundings of the reference's separate ops are the point)
 __device__ __forceinline__ gf_f32x2 ln2_mul(gf_f32x2 a, gf_f32x2 b) {
@@ -212,11 +224,13 @@ __device__ __forceinline__ gf_f32x2 ln2_add(gf_f32x2 a, gf_f32x2 b) {
     return a + b;
 }
 
-template <int NCH, int MODE, bool FP8>
+template <int NCH, int MODE, bool FP8, bool MX4 = false>
 __global__ __launch_bounds__(64 * WROWS) void layernorm_wave2_kernel(const u16* __restrict__ x, void* __restrict__ outp,
                                                                      float* __restrict__ scale_out, const u16* __restrict__ avec,
                                                                      const u16* __restrict__ bvec, long rows, long x_stride,
-                                                                     long out_stride, float eps) {
+                                                                     long out_stride, float eps,
+                                                                     unsigned char* __restrict__ mx_scales = nullptr, long mx_stride = 0) {
+    static_assert(!(FP8 && MX4), "one output kind");
     constexpr int DIM = NCH * 512;
     const long row = (long)blockIdx.x * WROWS + (threadIdx.x >> 6);
     if (row >= rows) return;
@@ -284,7 +298,12 @@ __global__ __launch_bounds__(64 * WROWS) void layernorm_wave2_kernel(const u16* 
             }
         }
         if constexpr (FP8) v[i] = o;            // the bf16 row fp8_linear receives, kept in registers
-        else *reinterpret_cast<u32x4*>((u16*)outp + row * out_stride + lane * 8 + i * 512) = o;
+        else if constexpr (MX4) {               // the whole wave is here (row is wave-uniform): every block's four lanes shuffle
+            int code;
+            const unsigned packed = mxfp4_block_step(__builtin_bit_cast(u16x8, o), code);
+            *reinterpret_cast<unsigned*>((unsigned char*)outp + row * out_stride + (c0 >> 1)) = packed;
+            if ((lane & 3) == 0) mx_scales[row * mx_stride + (c0 >> 5)] = (unsigned char)code;
+        } else *reinterpret_cast<u32x4*>((u16*)outp + row * out_stride + lane * 8 + i * 512) = o;
     }
     if constexpr (FP8) {
         float mx = bf2f(mxb[0] > mxb[1] ? mxb[0] : mxb[1]);
@@ -642,6 +661,50 @@ extern "C" GF_API int gf_layernorm_modulate_fp8(const void* x, void* out8, float
     GF_LN8_WAVE(10) GF_LN8_WAVE(8) GF_LN8_WAVE(3)
 #undef GF_LN8_WAVE
     GF_CHECK_LAUNCH("gf_layernorm_modulate_fp8");
+    return GF_OK;
+}
+
+extern "C" GF_API int gf_layernorm_modulate_mxfp4(const void* x, void* out4, void* scales, const void* weight, const void* bias,
+                                                  const void* scale1p, const void* shift, int64_t rows, int64_t dim, int64_t x_stride,
+                                                  int64_t out_stride, int64_t scale_stride, float eps, void* stream) {
+    GF_CHECK_ARG(x && out4 && scales, "gf_layernorm_modulate_mxfp4: null x/out4/scales");
+    GF_CHECK_ARG(rows >= 0 && (dim == 5120 || dim == 4096 || dim == 1536),
+                 "gf_layernorm_modulate_mxfp4: dim=%ld is not one of the wave-per-row widths (5120, 4096, 1536); use "
+                 "gf_layernorm_modulate + gf_quant_mxfp4", (long)dim);
+    GF_CHECK_ARG(x_stride % 8 == 0 && x_stride >= dim && out_stride % 4 == 0 && out_stride >= dim / 2 && scale_stride >= dim / 32,
+                 "gf_layernorm_modulate_mxfp4: strides must be multiples of 8 (x) / 4 (out4) and cover the row");
+    GF_CHECK_ARG(gf_aligned16(x) && (((uintptr_t)out4) & 3u) == 0,
+                 "gf_layernorm_modulate_mxfp4: rows must be 16-byte (x) / 4-byte (out4) aligned");
+    GF_CHECK_ARG((!weight || gf_aligned16(weight)) && (!bias || gf_aligned16(bias)) &&
+                     (!scale1p || gf_aligned16(scale1p)) && (!shift || gf_aligned16(shift)),
+                 "gf_layernorm_modulate_mxfp4: vectors must be 16-byte aligned");
+    if (rows == 0) return GF_OK;
+    const dim3 grid_((unsigned)((rows + WROWS - 1) / WROWS)), block_(64 * WROWS);
+    {
+        const int mode = (!weight && !bias && !scale1p && !shift) ? 0 : (weight && bias && !scale1p && !shift) ? 1
+                         : (!weight && !bias && scale1p && shift) ? 2 : -1;
+        const void* av = mode == 1 ? weight : scale1p;
+        const void* bv = mode == 1 ? bias : shift;
+#define GF_LN2(NCH, M)                                                                                                   \
+    if (dim == NCH * 512 && mode == M) {                                                                                 \
+        hipLaunchKernelGGL((layernorm_wave2_kernel<NCH, M, false, true>), grid_, block_, 0, (hipStream_t)stream, (const u16*)x,    \
+                           out4, (float*)nullptr, (const u16*)av, (const u16*)bv, (long)rows, (long)x_stride, (long)out_stride,  \
+                           eps, (unsigned char*)scales, (long)scale_stride);                                             \
+        GF_CHECK_LAUNCH("gf_layernorm_modulate_mxfp4");                                                                  \
+        return GF_OK;                                                                                                    \
+    }
+        GF_LN2(10, 0) GF_LN2(10, 1) GF_LN2(10, 2) GF_LN2(8, 0) GF_LN2(8, 1) GF_LN2(8, 2) GF_LN2(3, 0) GF_LN2(3, 1) GF_LN2(3, 2)
+#undef GF_LN2
+    }
+#define GF_LN4_WAVE(NCH)                                                                                                 \
+    if (dim == NCH * 512) {                                                                                              \
+        hipLaunchKernelGGL((layernorm_modulate_wave_kernel<NCH, true>), grid_, block_, 0, (hipStream_t)stream, (const u16*)x,      \
+                           (u16*)out4, (const u16*)weight, (const u16*)bias, (const u16*)scale1p, (const u16*)shift, (long)rows, \
+                           (long)x_stride, (long)out_stride, eps, (unsigned char*)scales, (long)scale_stride);           \
+    }
+    GF_LN4_WAVE(10) GF_LN4_WAVE(8) GF_LN4_WAVE(3)
+#undef GF_LN4_WAVE
+    GF_CHECK_LAUNCH("gf_layernorm_modulate_mxfp4");
     return GF_OK;
 }
 

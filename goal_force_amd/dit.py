@@ -238,7 +238,9 @@ def enable_fp4(module: nn.Module, enabled=True, layers=FP4_LAYERS):
     """MXFP4 linears (include/goalforce.h; the reference has no counterpart, off by default): the named Linears of every DiTBlock
     inside `module` (a block, a WanModel, a ControlNet or a whole pipeline) get an MXFP4 weight copy (ops.quant_mxfp4: e2m1 codes,
     one E8M0 scale per 32 input features) beside the bf16 master, and dit.linear runs them on ops.gemm_mxfp4 with the activation
-    quantised the same way per call.  "ffn" = ffn[0] and ffn[2], "o" = self_attn.o and cross_attn.o; q / k / v and the
+    quantised the same way per call — the "o" projections by the stand-alone pass, the FFN's two inputs inside the LayerNorm and
+    the GELU GEMM's epilogue (DiTBlock.forward; ops.options(fp4_fused=False): the stand-alone pass there too, the same bits).
+    "ffn" = ffn[0] and ffn[2], "o" = self_attn.o and cross_attn.o; q / k / v and the
     cross-attention's k / v keep their fused bf16 / fp8 paths and any other name is refused.  An fp4 copy wins over an fp8 copy of
     the same layer (enable_fp8); enabled=False removes the fp4 copies of the named layers and leaves whatever else was there.
     A mechanism: the quality of a trained model under it has not been measured."""
@@ -689,6 +691,16 @@ class DiTBlock(nn.Module):
             linear(a, ca.o, epilogue=ops.EPI_BIAS_RESID, resid=x_new, out=x_new)                        # DIT:227
         if keep is not None and keep.get("wide"):
             keep["x2b"] = x_new.clone()
+        if fp4_ffn and ops.option("fp4_fused"):
+            # the FFN under enable_fp4 in three launches: the LayerNorm and the GELU GEMM quantise what they hold in registers, so
+            # neither bf16 intermediate ([S, D], [S, F]) exists; the bits of the five-launch route below (ops.options(fp4_fused=False))
+            w0, w2 = fp4_weight(self.ffn[0]), fp4_weight(self.ffn[2])
+            assert w2 is not None, "enable_fp4 names ffn[0] and ffn[2] together"
+            h4, hs = ops.layernorm_modulate_mxfp4(x_new, scale1p=mod[4], shift=mod[3], eps=self.eps)      # DIT:228
+            f4, fs = ops.gemm_mxfp4_q4(h4, hs, w0[0], w0[1], self.ffn[0].bias, epilogue=ops.EPI_BIAS_GELU_TANH)
+            ops.gemm_mxfp4(f4, fs, w2[0], w2[1], self.ffn[2].bias, epilogue=ops.EPI_BIAS_GATE_RESID, resid=x_new, gate=mod[5],
+                           out=x_new)                                                                     # DIT:229
+            return x_new.view(x.shape)
         h = self._normed(x_new, fp8 and not fp4_ffn, None if fp8 else h, scale1p=mod[4], shift=mod[3])  # DIT:228
         f1 = linear(h, self.ffn[0], epilogue=ops.EPI_BIAS_GELU_TANH)
         linear(f1, self.ffn[2], epilogue=ops.EPI_BIAS_GATE_RESID, resid=x_new, gate=mod[5], out=x_new)  # DIT:229

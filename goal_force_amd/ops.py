@@ -289,11 +289,13 @@ VT_MIN_KV = 2048   # key sequences at least this long go through the pre-transpo
 #                attn_q_prescale (False: the self-attention's Q is rotated plainly and scaled inside the attention kernel — a second bf16 rounding),
 #                vae_attn_offset (False: the VAE attention's softmax on the bf16-rounded RAW scores — one GEMM instead of two, coarser),
 #                fold_cross_o (False: the cross-attention's output projection as attention + D->D GEMM instead of probabilities x the
-#                              folded value table, dit.CrossAttention.fold_ok)
+#                              folded value table, dit.CrossAttention.fold_ok),
+#                fp4_fused (False: the FFN of an enable_fp4 block as five launches — LayerNorm, quant_mxfp4, GEMM, quant_mxfp4, GEMM —
+#                           instead of three with the quantisation inside the LayerNorm and the GELU GEMM's epilogue; the same bits)
 _LIB_DEFAULTS = {"prefer_8wave": 0, "a4_stagger": 2, "a4_group_m": 0, "conv_nb": 0, "conv_gather": 0, "conv_direct": 1, "vae_rms3": 1,
                  "attn_fixed_max": 1}
 _OPT = {"attn_k3": True, "vt_from_gemm": True, "conv_padded": True, "fold_pad_keys": True, "attn_q_prescale": True, "vae_attn_offset": True,
-        "fold_cross_o": True}
+        "fold_cross_o": True, "fp4_fused": True}
 
 
 def option(name: str) -> bool:
@@ -1524,9 +1526,28 @@ def quant_mxfp4(x):
     return out, scale
 
 
-def gemm_mxfp4(a4, a_scale, w4, w_scale, bias=None, epilogue=EPI_BIAS, resid=None, gate=None, out=None):
-    """out[M,N] = epilogue(bf16(deq(a4, a_scale) @ deq(w4, w_scale)^T + bias)) — gf_gemm_mxfp4.  a4 [M,K/2] / w4 [N,K/2] uint8 packed
-    e2m1, a_scale [M,K/32] / w_scale [N,K/32] uint8 E8M0 (ops.quant_mxfp4); K % 256 == 0.  The checks and their words are _gemm's."""
+def layernorm_modulate_mxfp4(x, weight=None, bias=None, scale1p=None, shift=None, eps=1e-6):
+    """LayerNorm(+affine)(+modulate) straight into the fp4 Linear's input format: (x4 [M,K/2] uint8 packed e2m1, scale [M,K/32] uint8
+    E8M0) — gf_layernorm_modulate_mxfp4 at the DiT widths (the bf16 row never reaches HBM), elsewhere the two kernels it fuses; the
+    same bits either way."""
+    _req(x, "layernorm_modulate_mxfp4.x")
+    xv, rows, dim, xs = _rows2d(x, "layernorm_modulate_mxfp4.x")
+    if dim not in LN_FP8_WIDTHS:
+        return quant_mxfp4(layernorm_modulate(x, weight=weight, bias=bias, scale1p=scale1p, shift=shift, eps=eps))
+    _vec(weight, "layernorm_modulate_mxfp4.weight", dim)
+    _vec(bias, "layernorm_modulate_mxfp4.bias", dim)
+    _vec(scale1p, "layernorm_modulate_mxfp4.scale1p", dim)
+    _vec(shift, "layernorm_modulate_mxfp4.shift", dim)
+    out = torch.empty((rows, dim // 2), dtype=torch.uint8, device=x.device)
+    scale = torch.empty((rows, dim // 32), dtype=torch.uint8, device=x.device)
+    _lib.check(_lib.load().gf_layernorm_modulate_mxfp4(_ptr(xv), _ptr(out), _ptr(scale), _ptr(weight), _ptr(bias), _ptr(scale1p),
+                                                       _ptr(shift), rows, dim, xs, dim // 2, dim // 32, float(eps), _stream(x)),
+               "gf_layernorm_modulate_mxfp4")
+    return out, scale
+
+
+def _mxfp4_operands(a4, a_scale, w4, w_scale):
+    """The four operands of an fp4 GEMM, checked in gemm_mxfp4's words -> (M, N, K, ldw)."""
     _mat(a4, "mxfp4 linear: activation", torch.uint8)
     M, K2 = a4.shape
     K = 2 * K2
@@ -1537,6 +1558,35 @@ def gemm_mxfp4(a4, a_scale, w4, w_scale, bias=None, epilogue=EPI_BIAS, resid=Non
         _mat(t, name, torch.uint8)
         if tuple(t.shape) != (rows, K // 32):
             raise GoalForceError(f"{name}: expected [{rows}, {K // 32}], got {tuple(t.shape)}")
+    return M, N, K, ldw
+
+
+def gemm_mxfp4_q4(a4, a_scale, w4, w_scale, bias=None, epilogue=EPI_BIAS):
+    """(c4 [M,N/2], c_scale [M,N/32]) = quant_mxfp4(gemm_mxfp4(a4, a_scale, w4, w_scale, bias, epilogue)) in one launch —
+    gf_gemm_mxfp4_q4: the GEMM's epilogue quantises its finished bf16 values, which never reach HBM; the same bits as the two calls.
+    N % 32 == 0 and an epilogue without a second operand (EPI_BIAS, EPI_BIAS_GELU_TANH, EPI_BIAS_SILU); otherwise gemm_mxfp4's rules."""
+    if int(epilogue) not in (EPI_BIAS, EPI_BIAS_GELU_TANH, EPI_BIAS_SILU):
+        raise GoalForceError(f"gemm_mxfp4_q4: epilogue {int(epilogue)} is not one of EPI_BIAS, EPI_BIAS_GELU_TANH, EPI_BIAS_SILU: an epilogue "
+                             "with a residual operand is not quantised in the GEMM (use gemm_mxfp4 + quant_mxfp4)")
+    if torch.is_tensor(w4) and w4.dim() == 2 and w4.shape[0] % 32:
+        raise GoalForceError(f"gemm_mxfp4_q4: N = {w4.shape[0]} output features must be a multiple of 32 (one E8M0 scale per 32 columns)")
+    M, N, K, ldw = _mxfp4_operands(a4, a_scale, w4, w_scale)
+    _vec(bias, "gemm_mxfp4_q4.bias", N)
+    c4 = torch.empty((M, N // 2), dtype=torch.uint8, device=a4.device)
+    c_scale = torch.empty((M, N // 32), dtype=torch.uint8, device=a4.device)
+    if M == 0:                       # nothing to compute (an empty tensor has no address to hand over)
+        return c4, c_scale
+    with _timed(PROFILE_GEMM, M, N, K, int(epilogue)):
+        _lib.check(_lib.load().gf_gemm_mxfp4_q4(_ptr(a4), a4.stride(0), _ptr(a_scale), a_scale.stride(0), _ptr(w4), ldw, _ptr(w_scale),
+                                                w_scale.stride(0), _ptr(bias), _ptr(c4), N // 2, _ptr(c_scale), N // 32, M, N, K,
+                                                int(epilogue), _stream(a4)), "gf_gemm_mxfp4_q4")
+    return c4, c_scale
+
+
+def gemm_mxfp4(a4, a_scale, w4, w_scale, bias=None, epilogue=EPI_BIAS, resid=None, gate=None, out=None):
+    """out[M,N] = epilogue(bf16(deq(a4, a_scale) @ deq(w4, w_scale)^T + bias)) — gf_gemm_mxfp4.  a4 [M,K/2] / w4 [N,K/2] uint8 packed
+    e2m1, a_scale [M,K/32] / w_scale [N,K/32] uint8 E8M0 (ops.quant_mxfp4); K % 256 == 0.  The checks and their words are _gemm's."""
+    M, N, K, ldw = _mxfp4_operands(a4, a_scale, w4, w_scale)
     if out is None:
         out = torch.empty((M, N), dtype=_BF16, device=a4.device)
     ov, Mo, No, ldc = _rows2d(out, "gemm_mxfp4.out")

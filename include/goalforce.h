@@ -651,6 +651,29 @@ GF_API int gf_gemm_mxfp4(const void* A4, int64_t lda, const void* a_scale, int64
                          const void* w_scale, int64_t w_scale_stride, const void* bias, void* C, int64_t ldc, int64_t M, int64_t N,
                          int64_t K, int epilogue, const void* resid, int64_t ldr, const void* gate, void* stream);
 
+/* The two producers of an fp4 Linear's activation that quantise in the registers that hold the finished bf16 values, so that the bf16
+ * intermediate never reaches memory.  The block quantiser is one function (csrc/gf_mxfp4_quant.h) and works on bit patterns: both give
+ * the BYTES of the two-call path they replace (tests/test_fp4_fused_gpu.py: torch.equal on codes and scales).
+ *
+ * gf_layernorm_modulate_mxfp4 — gf_layernorm_modulate (its arithmetic and roundings, every subset of weight / bias / scale1p / shift)
+ * whose consumer is an fp4 Linear: out4 [rows, dim/2] packed e2m1 (row stride out_stride BYTES) and scales [rows, dim/32] E8M0 (row
+ * stride scale_stride bytes) = gf_quant_mxfp4 of the bf16 row gf_layernorm_modulate would have written.  dim must be one of the
+ * wave-per-row widths 5120 / 4096 / 1536; other widths: call the two functions.  x 16-byte aligned with x_stride % 8 == 0, the vectors
+ * 16-byte aligned, out4 4-byte aligned with out_stride % 4 == 0 (16 / 16 to serve as gf_gemm_mxfp4's A4); rows = 0 is a no-op. */
+GF_API int gf_layernorm_modulate_mxfp4(const void* x, void* out4, void* scales, const void* weight, const void* bias,
+                                       const void* scale1p, const void* shift, int64_t rows, int64_t dim, int64_t x_stride,
+                                       int64_t out_stride, int64_t scale_stride, float eps, void* stream);
+
+/* gf_gemm_mxfp4_q4 — C4 / c_scale = gf_quant_mxfp4(gf_gemm_mxfp4(...)) without C existing in memory: the epilogue's read-back quantises
+ * the finished bf16 values (activation and NaN-scale handling applied) 32 output columns at a time.  C4 [M, N/2] packed e2m1, 16-byte
+ * aligned, ldc4 in BYTES with ldc4 % 16 == 0 and ldc4 >= N/2 (a legal A4 of the next GEMM); c_scale [M, N/32] E8M0 with
+ * c_scale_stride >= N/32.  N % 32 == 0; the epilogues without a second operand only (GF_EPI_BIAS, GF_EPI_BIAS_GELU_TANH,
+ * GF_EPI_BIAS_SILU); every other operand rule is gf_gemm_mxfp4's.  A NaN output (a NaN scale in its row of A or of W) makes its block
+ * code 255 with zero elements, as gf_quant_mxfp4 does.  M = 0 is a no-op. */
+GF_API int gf_gemm_mxfp4_q4(const void* A4, int64_t lda, const void* a_scale, int64_t a_scale_stride, const void* W4, int64_t ldw,
+                            const void* w_scale, int64_t w_scale_stride, const void* bias, void* C4, int64_t ldc4, void* c_scale,
+                            int64_t c_scale_stride, int64_t M, int64_t N, int64_t K, int epilogue, void* stream);
+
 /* ------------------------------------------------------------------------
  * gf_conv3d_padded_bf16 — CausalConv3d 3x3x3, stride 1 (VAE:33-52) of the 192- and 384-channel levels of Decoder3d / Encoder3d
  * (VAE:736-838, 517-617) as a direct convolution on the 4-wave GEMM loop (gf_conv_a4.hip).

@@ -1,13 +1,19 @@
 #!/usr/bin/env python3
-"""MXFP4 linears against the fp8 and bf16 GEMMs of the same library, in ONE process, alternating (profiles/r15/README.md).
+"""MXFP4 linears against the fp8 and bf16 GEMMs of the same library, in ONE process, alternating (profiles/r15/README.md,
+profiles/r16/README.md).
 
   GEMM leg   M = 32760 at (N, K) = (13824, 5120), (5120, 13824), (5120, 5120): gf_gemm_mxfp4, its two quantiser passes' activation share
              (gf_quant_mxfp4 on [M, K]; the weight copy is made once, at enable_fp4) and, for the same accounting, gf_quant_fp8_rowscale,
              against gf_gemm_fp8 and gf_gemm_bf16; gf_gemm_fp8 twice (A/A) for the run-to-run spread.  Every variant is warmed, then
              timed in `--rounds` alternating rounds of `--calls` calls between two events; median, minimum and (max - min) / median.
+  producer   M = 32760: the two fused producers of the FFN's fp4 operands against the pairs they replace —
+  leg        layernorm_modulate(scale + shift) + quant_mxfp4 on [M, 5120] against layernorm_modulate_mxfp4, and gemm_mxfp4(GELU) at D->F +
+             quant_mxfp4 on [M, 13824] against gemm_mxfp4_q4; each pair timed as a pair, the pair twice (A/A) for the spread; the outputs
+             compared bit for bit.
   step leg   one high-noise step of the bench configuration (A14B experts, 10-layer ControlNets, 21 x 60 x 104 latents, CFG) under bf16,
-             fp8 (enable_fp8) and fp8 + enable_fp4(("ffn", "o")), alternating; then the latents after `--latent-steps` steps of each and
-             their rel-L2 from the bf16 latents.  Random-init weights: a number, not a quality claim.
+             fp8 (enable_fp8, twice: A/A), fp8 + enable_fp4(("ffn", "o")) with ops.options(fp4_fused=False) and the same fused,
+             alternating; then the latents after `--latent-steps` steps of each, their rel-L2 from the bf16 latents and whether the
+             fused and unfused latents are equal bit for bit.  Random-init weights: a number, not a quality claim.
 Prints one JSON line per leg; needs an MI355X (no fallback).
 """
 import argparse
@@ -86,7 +92,54 @@ def gemm_leg(torch, ops, rounds, calls):
     return out
 
 
+def producer_leg(torch, ops, rounds, calls):
+    g = torch.Generator(device="cuda").manual_seed(16)
+    x = torch.randn((S_TOKENS, DIM), device="cuda", generator=g).to(torch.bfloat16)
+    scale1p = (1 + 0.1 * torch.randn(DIM, device="cuda", generator=g)).to(torch.bfloat16)
+    shift = (0.1 * torch.randn(DIM, device="cuda", generator=g)).to(torch.bfloat16)
+    w4, ws = ops.quant_mxfp4((torch.randn((FFN, DIM), device="cuda", generator=g) / DIM ** 0.5).to(torch.bfloat16))
+    bias = (0.1 * torch.randn(FFN, device="cuda", generator=g)).to(torch.bfloat16)
+    h = torch.empty_like(x)
+    f = torch.empty((S_TOKENS, FFN), device="cuda", dtype=torch.bfloat16)
+    x4, xs = ops.quant_mxfp4(ops.layernorm_modulate(x, scale1p=scale1p, shift=shift, out=h))
+    gelu = ops.EPI_BIAS_GELU_TANH
+
+    def ln_pair():
+        return ops.quant_mxfp4(ops.layernorm_modulate(x, scale1p=scale1p, shift=shift, out=h))
+
+    def gemm_pair():
+        return ops.quant_mxfp4(ops.gemm_mxfp4(x4, xs, w4, ws, bias, epilogue=gelu, out=f))
+
+    variants = {
+        "ln_pair": ln_pair, "ln_fused": lambda: ops.layernorm_modulate_mxfp4(x, scale1p=scale1p, shift=shift), "ln_pair_again": ln_pair,
+        "gemm_pair": gemm_pair, "gemm_fused": lambda: ops.gemm_mxfp4_q4(x4, xs, w4, ws, bias, epilogue=gelu), "gemm_pair_again": gemm_pair,
+    }
+    same = {}
+    for name in ("ln", "gemm"):
+        (a4, a_s), (b4, b_s) = variants[name + "_pair"](), variants[name + "_fused"]()
+        same[name] = bool(torch.equal(a4, b4) and torch.equal(a_s, b_s))
+    times = {v: [] for v in variants}
+    for fn in variants.values():
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    for _ in range(rounds):
+        for v, fn in variants.items():
+            times[v].append(timed(torch, fn, calls))
+    res = {v: summary(t) for v, t in times.items()}
+    for name in ("ln", "gemm"):
+        pair, again, fused = (res[f"{name}_{v}"] for v in ("pair", "pair_again", "fused"))
+        aa = abs(pair["median_ms"] - again["median_ms"]) / pair["median_ms"]
+        noise = max(aa, pair["spread"], again["spread"])
+        res[name] = dict(bits_equal=same[name], aa_rel=round(aa, 4), noise_rel=round(noise, 4),
+                         pair_over_fused=round(pair["median_ms"] / fused["median_ms"], 3),
+                         saved_ms=round(pair["median_ms"] - fused["median_ms"], 4),
+                         fused_not_slower_beyond_noise=bool(fused["median_ms"] <= pair["median_ms"] * (1 + noise)))
+    return res
+
+
 def step_leg(torch, rounds, latent_steps, layers):
+    from goal_force_amd import ops
     from goal_force_amd import dit as D
     from goal_force_amd.pipeline import WanVideoPipeline, build_random_controlnet, build_random_expert
     dev = torch.device("cuda", 0)
@@ -112,34 +165,42 @@ def step_leg(torch, rounds, latent_steps, layers):
         for m in mods:
             D.enable_fp4(m, False)
             D.enable_fp8(m, mode != "bf16")
-            if mode == "fp8+fp4":
+            if mode.startswith("fp8+fp4"):
                 D.enable_fp4(m, True, layers=("ffn", "o"))
+        return ops.options(fp4_fused=not mode.endswith("unfused"))
 
     def run(ids, n_sched=50):
         return pipe.denoise(latents, ctx_p, ctx_n, y, control, num_inference_steps=n_sched, cfg_scale=5.0, controlnet=True, step_ids=ids,
                             record_step_times=True)
 
-    modes = ("bf16", "fp8", "fp8+fp4")
+    modes = ("bf16", "fp8", "fp8+fp4 unfused", "fp8+fp4 fused", "fp8 again")
     times = {m: [] for m in modes}
     for m in modes:                      # warm every mode
-        switch(m)
-        run([0])
+        with switch(m):
+            run([0])
     for _ in range(rounds):
         for m in modes:
-            switch(m)
-            run([0])
+            with switch(m):
+                run([0])
             times[m].append(pipe.last_step_ms[0][0])
     res = {m: summary(t) for m, t in times.items()}
-    noise = max(r["spread"] for r in res.values())
-    res["fp4_step_over_fp8_step"] = round(res["fp8"]["median_ms"] / res["fp8+fp4"]["median_ms"], 4)
-    res["fp4_step_faster_than_fp8_beyond_spread"] = bool(res["fp8+fp4"]["median_ms"] < res["fp8"]["median_ms"] * (1 - noise))
+    aa = abs(res["fp8"]["median_ms"] - res["fp8 again"]["median_ms"]) / res["fp8"]["median_ms"]
+    noise = max([aa] + [r["spread"] for r in res.values()])
+    res["aa_fp8_rel"], res["noise_rel"] = round(aa, 4), round(noise, 4)
+    fp8_ms, unfused_ms, fused_ms = (res[m]["median_ms"] for m in ("fp8", "fp8+fp4 unfused", "fp8+fp4 fused"))
+    res["fp8_step_over_fused_step"] = round(fp8_ms / fused_ms, 4)
+    res["fp8_step_over_unfused_step"] = round(fp8_ms / unfused_ms, 4)
+    res["unfused_step_over_fused_step"] = round(unfused_ms / fused_ms, 4)
+    res["fused_step_faster_than_fp8_beyond_spread"] = bool(fused_ms < fp8_ms * (1 - noise))
+    res["fused_step_faster_than_unfused_beyond_spread"] = bool(fused_ms < unfused_ms * (1 - noise))
     if latent_steps > 0:
         finals = {}
-        for m in modes:
-            switch(m)
-            finals[m] = pipe.denoise(latents, ctx_p, ctx_n, y, control, num_inference_steps=latent_steps, cfg_scale=5.0, controlnet=True).float()
-        ref = finals["bf16"]
-        res["latents_rel_l2_from_bf16"] = {m: round(float((finals[m] - ref).norm() / ref.norm()), 5) for m in modes[1:]}
+        for m in modes[:-1]:
+            with switch(m):
+                finals[m] = pipe.denoise(latents, ctx_p, ctx_n, y, control, num_inference_steps=latent_steps, cfg_scale=5.0, controlnet=True)
+        ref = finals["bf16"].float()
+        res["latents_rel_l2_from_bf16"] = {m: round(float((finals[m].float() - ref).norm() / ref.norm()), 5) for m in modes[1:-1]}
+        res["fused_latents_equal_unfused_bit_for_bit"] = bool(torch.equal(finals["fp8+fp4 fused"], finals["fp8+fp4 unfused"]))
         res["latent_steps"] = latent_steps
     switch("bf16")
     return res
@@ -152,14 +213,18 @@ def main():
     ap.add_argument("--step-rounds", type=int, default=3)
     ap.add_argument("--latent-steps", type=int, default=20)
     ap.add_argument("--layers", type=int, default=40)
-    ap.add_argument("--no-steps", action="store_true", help="the GEMM leg alone")
+    ap.add_argument("--no-steps", action="store_true", help="without the step leg")
+    ap.add_argument("--no-gemm", action="store_true", help="without the GEMM leg")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("fp4_ab.py measures on the GPU: no HIP device found (there is no fallback)")
     from goal_force_amd import ops
     torch.set_grad_enabled(False)
-    print(json.dumps({"leg": "gemm", "M": S_TOKENS, "rounds": args.rounds, "calls": args.calls, "shapes": gemm_leg(torch, ops, args.rounds, args.calls)}), flush=True)
+    if not args.no_gemm:
+        print(json.dumps({"leg": "gemm", "M": S_TOKENS, "rounds": args.rounds, "calls": args.calls, "shapes": gemm_leg(torch, ops, args.rounds, args.calls)}), flush=True)
+    print(json.dumps({"leg": "producer", "M": S_TOKENS, "rounds": args.rounds, "calls": args.calls, **producer_leg(torch, ops, args.rounds, args.calls)}), flush=True)
+    torch.cuda.empty_cache()
     if not args.no_steps:
         print(json.dumps({"leg": "step", "rounds": args.step_rounds, **step_leg(torch, args.step_rounds, args.latent_steps, args.layers)}), flush=True)
 
