@@ -7,7 +7,8 @@ GEMM epilogue, in-place residuals — and reports every case whose error exceeds
 refusal the header documents.  Exit code 1 when anything failed.  `--only fwdrows` (not part of the default sweep) holds the forward
 row kernels against the exact chains of tests/forward_refs.py, `--only attnfwd` (opt-in as well) the attention forward's entry points
 against the bounds of tests/attention_fwd_refs.py, `--only gemmpin` (opt-in) the GEMM family against the exact chain and the two bars
-of tests/gemm_refs.py."""
+of tests/gemm_refs.py, `--only vaepin` (opt-in) the VAE's convolution kernels against the plain fp64 convolution of tests/vae_refs.py
+through the same bars."""
 import argparse
 import math
 import os
@@ -479,9 +480,94 @@ def case_gemmpin(rnd, g):
     return desc + f" | {differing} elements differ", (math.inf if differing else 0.0), 1.0
 
 
-CASES = {"gemmpin": case_gemmpin, "gemm": case_gemm, "attn": case_attn, "rows": case_rows, "cfg": case_cfg, "attnbwd": case_attnbwd, "fp8": case_fp8,
+def case_vaepin(rnd, g):
+    """The VAE's convolution kernels pinned as tests/test_vae_pinned_gpu.py pins them (helpers: tests/vae_refs.py), at random geometry:
+    mode 0 / 1 / 2, kt and ks 1 or 3, a random temporal window (t_stride 2 for the time convolution), a random kernel route — the
+    general gather (separate cache or conv_gather = 1), the pointer-per-row gather (history in front), the direct 96-channel and
+    upsample kernels at their shapes, the padded-layout kernel — one of the three data classes, either epilogue, inside NaN-filled
+    parents.  integers / selector: any differing bit is an error; gauss: the largest of the differing share over 2^-10 (any differing
+    element below 1024 elements), the worst row / column count over its binomial cap and the worst element's share of
+    2^-7 m + K 2^-23 S; bar 1."""
+    if os.path.join(ROOT, "tests") not in sys.path:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import gemm_refs as R
+    import vae_refs as V
+    cls = rnd.choice(V.CLASSES)
+    route = rnd.choice(["general", "general", "ptr", "ptr", "c96", "up", "padded"])
+    epi = rnd.choice(V.EPIS)
+    H, W = rnd.choice([1, 2, 7, 8, 9, 16, 17, 31, 33]), rnd.choice([1, 2, 15, 16, 17, 32, 33, 65])
+    t_out, off = rnd.randrange(1, 5), rnd.choice([0, 0, 1, 2])
+    N = 8 * rnd.choice([1, 2, 3, 12, 16, 17, 24, 25, 33, 48])
+    kw = dict(hist=rnd.random() < 0.8, seed=rnd.randrange(1000))
+    if route == "c96":
+        c = V._c(route, off + t_out, H, W, 96, rnd.choice([96, 96, 8, 16]), 3, 3, t_off=off, t_out=t_out, **kw)
+    elif route == "up":
+        c = V._c(route, off + t_out, 4 * rnd.randrange(1, 4), 16 * rnd.randrange(1, 3), 192, 96, 1, 3, mode=1, t_off=off, t_out=t_out, **kw)
+    elif route == "padded":
+        kt = rnd.choice([1, 3])
+        c = V._c(route, t_out, H, min(W, 33), rnd.choice([192, 384]), N, kt, 3, hist=kt == 3 and kw["hist"], seed=kw["seed"])
+    else:
+        kt, ks = rnd.choice([(3, 3), (1, 3), (3, 1), (1, 1)])
+        mode = rnd.choice([0, 0, 1, 2]) if (route == "general" and ks == 3) else 0
+        ts = 2 if (kt == 3 and ks == 1 and rnd.random() < 0.5) else 1
+        if mode == 2:
+            H, W = 2 * H, 2 * W
+        c = V._c(route, off + (t_out - 1) * ts + 1 + rnd.randrange(0, 2), H, W, rnd.choice([8, 24, 64, 96, 192]), N, kt, ks, mode=mode, t_stride=ts,
+                 t_off=off, t_out=t_out, **kw)
+    while V._flops(c) > V.FLOP_CAP:                # keep the fp64 reference affordable: fewer frames on the direct kernels, else fewer columns
+        if route in ("c96", "up") and c["t_out"] > 1:
+            c = dict(c, T=c["T"] - 1, t_out=c["t_out"] - 1)
+        elif route not in ("c96", "up") and c["N"] > 8:
+            c = dict(c, N=max(8, c["N"] // 2 // 8 * 8))
+        else:
+            break
+    Ho, Wo = V.out_hw(c["H"], c["W"], c.get("mode", 0))
+    while cls == "gauss" and route in ("general", "ptr", "padded") and 400 < c.get("t_out", c["T"]) * Ho * Wo * c["N"] < 1024:
+        c = dict(c, N=c["N"] + 8)                  # (below 1024 outputs every element must be drawn clear of the rounding boundaries: few draws are)
+    d = V.case_inputs(c, cls)
+    T, Hh, Ww, C, Nn = d["shape"]
+    dev = lambda t: None if t is None else t.cuda()          # noqa: E731
+    resid = dev(d["resid"]) if epi == R.EPI_RESID else None
+    if route == "padded":
+        parent = torch.full((d["kt"] + 1 + T, Hh + 2, Ww + 2, C), float("nan"), dtype=BF, device="cuda")
+        buf = parent[1:d["kt"] + T]
+        buf.zero_()
+        if d["kt"] == 3 and d["hist"] is not None:
+            buf[:2, 1:Hh + 1, 1:Ww + 1] = dev(d["hist"])
+        buf[d["kt"] - 1:, 1:Hh + 1, 1:Ww + 1] = dev(d["x"])
+        got = ops.vae_conv3d_padded(buf, dev(d["w"]), dev(d["bias"]), resid=resid, kt=d["kt"])
+    else:
+        parent = torch.full((T + 4, Hh, Ww, C), float("nan"), dtype=BF, device="cuda")
+        read = set(V.frames_read(d["kt"], d["t_stride"], d["t_off"], d["t_out"]))
+        for f in range(T):
+            if f in read:
+                parent[3 + f] = dev(d["x"][f])
+        cache, front = None, False
+        if d["kt"] == 3:
+            h = dev(torch.zeros((2, Hh, Ww, C), dtype=BF) if d["hist"] is None else d["hist"])
+            if route == "general":
+                cache = h.clone()
+            else:
+                parent[1:3], front = h, True
+        opts = dict(conv_direct=int(route in ("c96", "up")), conv_gather=int(route == "general"))
+        with ops.options(**opts):
+            got = ops.vae_conv3d(parent[3:3 + T], cache, dev(d["w"]), dev(d["bias"]), d["kt"], d["ks"], upsample2x=d["mode"] == 1, downsample2=d["mode"] == 2,
+                                 t_stride=d["t_stride"], t_off=d["t_off"], t_out=d["t_out"], resid=resid, history_in_front=front)
+    torch.cuda.synchronize()
+    got = got.cpu()
+    ref = V.conv_ref(d, epi)
+    desc = f"vaepin {V.case_id(c)} {cls} {R.EPI_NAMES[epi]}"
+    if cls == "gauss":
+        j = R.judge(got, ref, V.conv_k(d))
+        a_err = (math.inf if j["differing"] else 0.0) if R.SHARE_CAP * j["numel"] < 1 else j["share"] / R.SHARE_CAP
+        return desc + " | " + R.describe(j), max(a_err, j["row_worst"] / j["row_cap"], j["col_worst"] / j["col_cap"], j["worst"]), 1.0
+    differing = int((R.bits(got) != R.bits(ref.out)).sum())
+    return desc + f" | {differing} elements differ", (math.inf if differing else 0.0), 1.0
+
+
+CASES = {"gemmpin": case_gemmpin, "vaepin": case_vaepin, "gemm": case_gemm, "attn": case_attn, "rows": case_rows, "cfg": case_cfg, "attnbwd": case_attnbwd, "fp8": case_fp8,
          "batched": case_batched, "misc": case_misc, "bwdrows": case_bwdrows, "fwdrows": case_fwdrows, "attnfwd": case_attnfwd}
-OPT_IN = ("fwdrows", "attnfwd", "gemmpin")       # run with --only alone (bwdrows is in the default sweep): the default sweep, and the suite's run of it, stays what it was
+OPT_IN = ("fwdrows", "attnfwd", "gemmpin", "vaepin")       # run with --only alone (bwdrows is in the default sweep): the default sweep, and the suite's run of it, stays what it was
 
 
 def main():
