@@ -35,25 +35,25 @@ constexpr int K3_DMA0 = 10;      // slot of the phase's first staging piece ...
 constexpr int K3_DMAS = 8;       // ... and the slot distance between pieces (4 per wave and phase)
 
 struct AttnArgs {
-    const u16* q;
-    const u16* k;
-    const u16* v;
-    u16* o;
-    int q_len, kv_len, heads, n_qblocks;
-    long q_stride, k_stride, v_stride, o_stride;
-    float scale_log2e;  // softmax scale * log2(e)
-    unsigned long long* dbg;   // unused (kept so that diagnostic builds from tools/patches need no ABI change inside the library)
-    float* lse;         // optional [q_len, heads] fp32: log2-domain log-sum-exp of the scaled scores (training backward)
-    const u16* vt;      // kernel 2, VT form: V^T [heads][128][kv_pad] from gf_transpose_v (keys permuted inside 16-groups)
-    long kv_pad;
-    float last_key_bias;   // kernel 2 (gf_flash_attn_fwd_lastmult): added to the RAW scores of key kv_len - 1 = log2(multiplicity) / (scale log2 e):
-                           // that key then counts `multiplicity` times in the softmax — a run of identical trailing keys folded into one
+    const u16* q = nullptr;
+    const u16* k = nullptr;
+    const u16* v = nullptr;
+    u16* o = nullptr;
+    int q_len = 0, kv_len = 0, heads = 0, n_qblocks = 0;
+    long q_stride = 0, k_stride = 0, v_stride = 0, o_stride = 0;
+    float scale_log2e = 0.f;   // softmax scale * log2(e)
+    unsigned long long* dbg = nullptr;   // unused (kept so that diagnostic builds from tools/patches need no ABI change inside the library)
+    float* lse = nullptr;      // optional [q_len, heads] fp32: log2-domain log-sum-exp of the scaled scores (training backward)
+    const u16* vt = nullptr;   // kernel 2, VT form: V^T [heads][128][kv_pad] from gf_transpose_v (keys permuted inside 16-groups)
+    long kv_pad = 0;
+    float last_key_bias = 0.f;   // kernel 2 (gf_flash_attn_fwd_lastmult): added to the RAW scores of key kv_len - 1 = log2(multiplicity) / (scale log2 e):
+                                 // that key then counts `multiplicity` times in the softmax — a run of identical trailing keys folded into one
     // kernel 3, sparse instantiation only (gf_flash_attn_fwd_vt32_sparse): the key tiles every query block visits, CSR
-    const int* row_ptr;    // [n_maps * n_qblocks + 1]
-    const int* tile_idx;   // ascending inside a row
-    const int* head_map;   // [heads] or NULL (every head: map 0)
-    int n_maps;
-    int* flags;            // kernel 3, fixed-max and repair modes: [heads * n_qblocks * 8], one word per wave (K3_FIXED writes, K3_REPAIR reads)
+    const int* row_ptr = nullptr;    // [n_maps * n_qblocks + 1]
+    const int* tile_idx = nullptr;   // ascending inside a row
+    const int* head_map = nullptr;   // [heads] or NULL (every head: map 0)
+    int n_maps = 0;
+    int* flags = nullptr;            // kernel 3, fixed-max and repair modes: [heads * n_qblocks * 8], one word per wave (K3_FIXED writes, K3_REPAIR reads)
 };
 
 // ================================================================================================================
@@ -1161,32 +1161,29 @@ __global__ __launch_bounds__(256) void transpose_v_kernel(const u16* __restrict_
 
 }  // namespace
 
-static int flash_attn_fwd_impl(const void* q, const void* k, const void* v, void* o, float* lse, int64_t q_len, int64_t kv_len,
-                               int64_t heads, int64_t head_dim, int64_t q_stride, int64_t k_stride,
-                               int64_t v_stride, int64_t o_stride, float scale, void* stream, const void* vt = nullptr,
-                               int64_t kv_pad = 0, float last_key_multiplicity = 1.0f) {
-    if (vt) {   // pre-transposed V: v itself is not read
-        v = k;
-        v_stride = k_stride;
-    }
-    GF_CHECK_ARG(q && k && v && o, "gf_flash_attn_fwd: null pointer");
+// What kernel 2 and kernel 3 ask of their operands, in the order both have always answered in, and the one place an AttnArgs is filled.
+// `fn` names the entry point in the messages (kernel 2: always "gf_flash_attn_fwd").  k3: V is read from `vt` alone (v = k on entry), at
+// least two key tiles, and the V^T buffer's rule sits between the lengths and the strides; kernel 2's V^T entry states that rule itself.
+static int attn_check_args(AttnArgs& a, const char* fn, bool k3, const void* q, const void* k, const void* v, const void* vt, void* o, float* lse,
+                           int64_t q_len, int64_t kv_len, int64_t kv_pad, int64_t heads, int64_t head_dim, int64_t q_stride, int64_t k_stride,
+                           int64_t v_stride, int64_t o_stride, float scale) {
+    const void* vop = k3 ? vt : v;   // the operand V is read from
+    GF_CHECK_ARG(q && k && vop && o, "%s: null pointer", fn);
     if (head_dim != HD) {
-        gf_set_error("gf_flash_attn_fwd: head_dim=%ld unsupported (kernel is built for 128)", (long)head_dim);
+        gf_set_error("%s: head_dim=%ld unsupported (kernel is built for 128)", fn, (long)head_dim);
         return GF_ERR_UNSUPPORTED;
     }
-    GF_CHECK_ARG(q_len >= 0 && kv_len > 0 && heads > 0, "gf_flash_attn_fwd: bad lengths q=%ld kv=%ld heads=%ld",
-                 (long)q_len, (long)kv_len, (long)heads);
+    GF_CHECK_ARG(q_len >= 0 && kv_len >= (k3 ? 2 * KVB : 1) && heads > 0 && (!k3 || (q_len < (1 << 30) && kv_len < (1 << 30))),
+                 "%s: bad lengths q=%ld kv=%ld heads=%ld%s", fn, (long)q_len, (long)kv_len, (long)heads, k3 ? " (kv_len >= 128)" : "");
+    GF_CHECK_ARG(!k3 || (kv_pad >= kv_len && kv_pad % KVB == 0 && heads * HD * kv_pad < (1LL << 31)), "%s: bad V^T buffer", fn);
     GF_CHECK_ARG(q_stride % 8 == 0 && k_stride % 8 == 0 && v_stride % 8 == 0 && o_stride % 4 == 0 &&
                      q_stride >= heads * HD && k_stride >= heads * HD && v_stride >= heads * HD &&
                      o_stride >= heads * HD,
-                 "gf_flash_attn_fwd: strides must cover heads*128 and be multiples of 8");
-    GF_CHECK_ARG(gf_aligned16(q) && gf_aligned16(k) && gf_aligned16(v) && gf_aligned16(o),
-                 "gf_flash_attn_fwd: 16-byte alignment required");
-    GF_CHECK_ARG(q_len < (1 << 30) && kv_len < (1 << 30), "gf_flash_attn_fwd: sequence too long");
+                 "%s: strides must cover heads*128 and be multiples of 8", fn);
+    GF_CHECK_ARG(gf_aligned16(q) && gf_aligned16(k) && gf_aligned16(vop) && gf_aligned16(o), "%s: 16-byte alignment required", fn);
+    GF_CHECK_ARG(q_len < (1 << 30) && kv_len < (1 << 30), "%s: sequence too long", fn);   // kernel 3 has answered this with its lengths
     GF_CHECK_ARG((kv_len + 64) * k_stride < (1LL << 31) && (kv_len + 64) * v_stride < (1LL << 31),
-                 "gf_flash_attn_fwd: kv_len*stride must stay below 2^31 elements");
-    if (q_len == 0) return GF_OK;
-    AttnArgs a;
+                 "%s: kv_len*stride must stay below 2^31 elements", fn);
     a.q = (const u16*)q;
     a.k = (const u16*)k;
     a.v = (const u16*)v;
@@ -1203,13 +1200,27 @@ static int flash_attn_fwd_impl(const void* q, const void* k, const void* v, void
     a.lse = lse;
     a.vt = (const u16*)vt;
     a.kv_pad = kv_pad;
-    a.last_key_bias = 0.f;
+    return GF_OK;
+}
+
+static int flash_attn_fwd_impl(const void* q, const void* k, const void* v, void* o, float* lse, int64_t q_len, int64_t kv_len,
+                               int64_t heads, int64_t head_dim, int64_t q_stride, int64_t k_stride,
+                               int64_t v_stride, int64_t o_stride, float scale, void* stream, const void* vt = nullptr,
+                               int64_t kv_pad = 0, float last_key_multiplicity = 1.0f) {
+    if (vt) {   // pre-transposed V: v itself is not read
+        v = k;
+        v_stride = k_stride;
+    }
+    AttnArgs a;
+    if (const int rc = attn_check_args(a, "gf_flash_attn_fwd", false, q, k, v, vt, o, lse, q_len, kv_len, kv_pad, heads, head_dim, q_stride,
+                                       k_stride, v_stride, o_stride, scale))
+        return rc;
+    if (q_len == 0) return GF_OK;
     if (last_key_multiplicity != 1.0f) {
         GF_CHECK_ARG(last_key_multiplicity >= 1.0f && !vt && scale > 0.f,
                      "gf_flash_attn_fwd_lastmult: multiplicity >= 1, plain-V form only (not the V^T form)");
         a.last_key_bias = log2f(last_key_multiplicity) / a.scale_log2e;
     }
-    a.dbg = nullptr;
     const dim3 grid((unsigned)(a.n_qblocks * a.heads)), block(AT2_THREADS);
     const char* fn = "gf_flash_attn_fwd";
     return vt ? gf_launch_lds<flash_attn_fwd_kernel2<true>>(fn, GF_ATTR_MSG_PLAIN, fn, grid, block, AT2_LDS, (hipStream_t)stream, a)
@@ -1238,17 +1249,24 @@ extern "C" GF_API int gf_flash_attn_fwd_lse(const void* q, const void* k, const 
                                stream);
 }
 
+// gf_transpose_v / gf_transpose_v32: the same operands and rules, the key order inside a tile is the kernel's
+template <auto Kernel>
+static int transpose_v_impl(const char* fn, const void* v, int64_t v_stride, void* vt, int64_t kv_len, int64_t kv_pad, int64_t heads,
+                            void* stream) {
+    GF_CHECK_ARG(v && vt, "%s: null pointer", fn);
+    GF_CHECK_ARG(kv_len > 0 && heads > 0 && kv_pad >= kv_len && kv_pad % KVB == 0 && v_stride % 8 == 0 && v_stride >= heads * HD,
+                 "%s: kv_pad must be a multiple of 64 covering kv_len; v_stride must cover heads*128", fn);
+    GF_CHECK_ARG(gf_aligned16(v) && gf_aligned16(vt), "%s: 16-byte alignment required", fn);
+    GF_CHECK_ARG(heads * HD * kv_pad < (1LL << 31), "%s: heads*128*kv_pad must stay below 2^31 elements", fn);
+    hipLaunchKernelGGL(Kernel, dim3((unsigned)(kv_pad / KVB), (unsigned)heads), dim3(256), 0, (hipStream_t)stream, (const u16*)v, (u16*)vt,
+                       (int)kv_len, (long)kv_pad, (long)v_stride);
+    GF_CHECK_LAUNCH(fn);
+    return GF_OK;
+}
+
 extern "C" GF_API int gf_transpose_v(const void* v, int64_t v_stride, void* vt, int64_t kv_len, int64_t kv_pad, int64_t heads,
                                      void* stream) {
-    GF_CHECK_ARG(v && vt, "gf_transpose_v: null pointer");
-    GF_CHECK_ARG(kv_len > 0 && heads > 0 && kv_pad >= kv_len && kv_pad % KVB == 0 && v_stride % 8 == 0 && v_stride >= heads * HD,
-                 "gf_transpose_v: kv_pad must be a multiple of 64 covering kv_len; v_stride must cover heads*128");
-    GF_CHECK_ARG(gf_aligned16(v) && gf_aligned16(vt), "gf_transpose_v: 16-byte alignment required");
-    GF_CHECK_ARG(heads * HD * kv_pad < (1LL << 31), "gf_transpose_v: heads*128*kv_pad must stay below 2^31 elements");
-    hipLaunchKernelGGL(transpose_v_kernel, dim3((unsigned)(kv_pad / KVB), (unsigned)heads), dim3(256), 0, (hipStream_t)stream,
-                       (const u16*)v, (u16*)vt, (int)kv_len, (long)kv_pad, (long)v_stride);
-    GF_CHECK_LAUNCH("gf_transpose_v");
-    return GF_OK;
+    return transpose_v_impl<transpose_v_kernel>("gf_transpose_v", v, v_stride, vt, kv_len, kv_pad, heads, stream);
 }
 
 extern "C" GF_API int gf_flash_attn_fwd_vt(const void* q, const void* k, const void* vt, void* o, float* lse, int64_t q_len,
@@ -1262,15 +1280,7 @@ extern "C" GF_API int gf_flash_attn_fwd_vt(const void* q, const void* k, const v
 
 extern "C" GF_API int gf_transpose_v32(const void* v, int64_t v_stride, void* vt, int64_t kv_len, int64_t kv_pad, int64_t heads,
                                        void* stream) {
-    GF_CHECK_ARG(v && vt, "gf_transpose_v32: null pointer");
-    GF_CHECK_ARG(kv_len > 0 && heads > 0 && kv_pad >= kv_len && kv_pad % KVB == 0 && v_stride % 8 == 0 && v_stride >= heads * HD,
-                 "gf_transpose_v32: kv_pad must be a multiple of 64 covering kv_len; v_stride must cover heads*128");
-    GF_CHECK_ARG(gf_aligned16(v) && gf_aligned16(vt), "gf_transpose_v32: 16-byte alignment required");
-    GF_CHECK_ARG(heads * HD * kv_pad < (1LL << 31), "gf_transpose_v32: heads*128*kv_pad must stay below 2^31 elements");
-    hipLaunchKernelGGL(transpose_v32_kernel, dim3((unsigned)(kv_pad / KVB), (unsigned)heads), dim3(256), 0, (hipStream_t)stream,
-                       (const u16*)v, (u16*)vt, (int)kv_len, (long)kv_pad, (long)v_stride);
-    GF_CHECK_LAUNCH("gf_transpose_v32");
-    return GF_OK;
+    return transpose_v_impl<transpose_v32_kernel>("gf_transpose_v32", v, v_stride, vt, kv_len, kv_pad, heads, stream);
 }
 
 // gf_flash_attn_fwd_vt32 (row_ptr NULL: the dense instantiation) and gf_flash_attn_fwd_vt32_sparse: one set of checks, one launch
@@ -1284,44 +1294,16 @@ static int flash_attn_vt32_impl(const char* fn, int32_t* flags, const void* q, c
                                 const int32_t* tile_idx, const int32_t* head_map, int64_t n_maps, int64_t q_len, int64_t kv_len,
                                 int64_t kv_pad, int64_t heads, int64_t head_dim, int64_t q_stride, int64_t k_stride, int64_t o_stride,
                                 float scale, void* stream) {
-    GF_CHECK_ARG(q && k && vt && o, "%s: null pointer", fn);
-    if (head_dim != HD) {
-        gf_set_error("%s: head_dim=%ld unsupported (kernel is built for 128)", fn, (long)head_dim);
-        return GF_ERR_UNSUPPORTED;
-    }
-    GF_CHECK_ARG(q_len >= 0 && kv_len >= 2 * KVB && heads > 0 && q_len < (1 << 30) && kv_len < (1 << 30),
-                 "%s: bad lengths q=%ld kv=%ld heads=%ld (kv_len >= 128)", fn, (long)q_len, (long)kv_len, (long)heads);
-    GF_CHECK_ARG(kv_pad >= kv_len && kv_pad % KVB == 0 && heads * HD * kv_pad < (1LL << 31), "%s: bad V^T buffer", fn);
-    GF_CHECK_ARG(q_stride % 8 == 0 && k_stride % 8 == 0 && o_stride % 4 == 0 && q_stride >= heads * HD && k_stride >= heads * HD &&
-                     o_stride >= heads * HD,
-                 "%s: strides must cover heads*128 and be multiples of 8", fn);
-    GF_CHECK_ARG(gf_aligned16(q) && gf_aligned16(k) && gf_aligned16(vt) && gf_aligned16(o), "%s: 16-byte alignment required", fn);
-    GF_CHECK_ARG((kv_len + 64) * k_stride < (1LL << 31), "%s: kv_len*stride must stay below 2^31 elements", fn);
+    AttnArgs a;
+    if (const int rc = attn_check_args(a, fn, true, q, k, k, vt, o, lse, q_len, kv_len, kv_pad, heads, head_dim, q_stride, k_stride, k_stride,
+                                       o_stride, scale))
+        return rc;
     const bool sparse = row_ptr != nullptr;
     const int64_t n_qblocks = (q_len + QB - 1) / QB;
     if (sparse)
         GF_CHECK_ARG(n_maps >= 1 && n_maps * n_qblocks < (1LL << 31) - 1, "%s: n_maps=%ld (at least 1; n_maps * query blocks below 2^31)", fn,
                      (long)n_maps);
     if (q_len == 0) return GF_OK;
-    AttnArgs a;
-    a.q = (const u16*)q;
-    a.k = (const u16*)k;
-    a.v = (const u16*)k;
-    a.o = (u16*)o;
-    a.q_len = (int)q_len;
-    a.kv_len = (int)kv_len;
-    a.heads = (int)heads;
-    a.n_qblocks = (int)n_qblocks;
-    a.q_stride = q_stride;
-    a.k_stride = k_stride;
-    a.v_stride = k_stride;
-    a.o_stride = o_stride;
-    a.scale_log2e = scale * 1.4426950408889634f;
-    a.lse = lse;
-    a.vt = (const u16*)vt;
-    a.kv_pad = kv_pad;
-    a.dbg = nullptr;
-    a.last_key_bias = 0.f;
     a.row_ptr = row_ptr;
     a.tile_idx = tile_idx;
     a.head_map = head_map;

@@ -40,35 +40,36 @@ constexpr int GROUP_M = 8;           // 16: -14 % (18 instead of 12 operand slic
 // gf_vae.hip's im2col_kernel (same modes), and every 16-byte LDS-DMA piece (8 channels of one tap of one pixel) is fetched
 // straight from the channels-last activation [T, H, W, C] (or the 2-frame causal cache, or a zero page for padding).
 struct ConvGeom {
-    const u16* src;     // [T_in, H, W, C]
-    const u16* cache;   // [2, H, W, C]: frames -2, -1 (kt == 3)
-    const u16* zero;    // >= 16 zero bytes
-    int H, W, C, Ho, Wo, kt, ks, mode, t_stride, t_off, taps;
-    int hist_front;     // kt == 3 without `cache`: frames -2, -1 lie directly in front of src (one [2 + T, H, W, C] buffer)
-    int c64;            // C % 64 == 0 and no K padding: a 64-channel K tile lies inside ONE tap (the tap arithmetic is then scalar)
-    long frame;         // H*W*C
-    float inv_c, inv_ks2;
+    const u16* src = nullptr;     // [T_in, H, W, C]
+    const u16* cache = nullptr;   // [2, H, W, C]: frames -2, -1 (kt == 3)
+    const u16* zero = nullptr;    // >= 16 zero bytes
+    int H = 0, W = 0, C = 0, Ho = 0, Wo = 0, kt = 0, ks = 0, mode = 0, t_stride = 0, t_off = 0, taps = 0;
+    int hist_front = 0; // kt == 3 without `cache`: frames -2, -1 lie directly in front of src (one [2 + T, H, W, C] buffer)
+    int c64 = 0;        // C % 64 == 0 and no K padding: a 64-channel K tile lies inside ONE tap (the tap arithmetic is then scalar)
+    long frame = 0;     // H*W*C
+    float inv_c = 0.f, inv_ks2 = 0.f;
 };
 
+// Every field starts defined: the struct goes to the kernels by value, whichever fields an entry point has a use for.
 struct GemmArgs {
-    const u16* A;
-    const u16* W;
-    const u16* bias;
-    u16* C;
-    const u16* R;
-    const u16* gate;
-    const float* row_scale;  // FP8 only: per-row dequant scale of A (gf_quant_fp8_rowscale)
-    int M, N, K;
-    long lda, ldw, ldc, ldr;
+    const u16* A = nullptr;
+    const u16* W = nullptr;
+    const u16* bias = nullptr;
+    u16* C = nullptr;
+    const u16* R = nullptr;
+    const u16* gate = nullptr;
+    const float* row_scale = nullptr;  // FP8 only: per-row dequant scale of A (gf_quant_fp8_rowscale)
+    int M = 0, N = 0, K = 0;
+    long lda = 0, ldw = 0, ldc = 0, ldr = 0;
     long sA = 0, sW = 0, sC = 0;   // gf_gemm_bf16_batched (gemm_ph_kernel, blockIdx.y = batch index): element strides between the problems
-    int tiles_m, tiles_n;
+    int tiles_m = 0, tiles_n = 0;
     unsigned long long* rsv0 = nullptr;   // reserved: the kernarg layout the shipped kernels were scheduled and measured with is kept
     ConvGeom cv;
     int rsv1 = 0;
-    int stagger;  // gemm_a4_kernel: column tile j starts its K loop at K tile (stagger * j) mod nk (option "a4_stagger", default 2; 0 = off)
-    int wrows;    // gemm_a4_kernel: rows of W that exist (= N except for GF_EPI_VT32, where N = kv_pad covers zero columns past kv_len)
-    int stagger_rows;   // gemm_a4_kernel: the K-loop rotation follows the ROW tile (GF_EPI_VT32: the operands are swapped, see gf_linear_vt32)
-    int group_m;        // gemm_a4_kernel: row tiles per workgroup-order group (set by launch_gemm_a4)
+    int stagger = 0;  // gemm_a4_kernel: column tile j starts its K loop at K tile (stagger * j) mod nk (option "a4_stagger", default 2; 0 = off)
+    int wrows = 0;    // gemm_a4_kernel: rows of W that exist (= N except for GF_EPI_VT32, where N = kv_pad covers zero columns past kv_len)
+    int stagger_rows = 0;   // gemm_a4_kernel: the K-loop rotation follows the ROW tile (GF_EPI_VT32: the operands are swapped, see linear_vt32_impl)
+    int group_m = 0;        // gemm_a4_kernel: row tiles per workgroup-order group (set by launch_gemm_a4)
     int rsv2 = 0;
 };
 
@@ -77,18 +78,6 @@ struct GemmArgs {
 constexpr int GF_EPI_VT32 = 6;
 
 typedef __attribute__((ext_vector_type(8))) int i32x8;
-
-// The Linear's own output is rounded to bf16 before anything else happens to it.  Where the epilogue applies a function to it
-// (GELU, SiLU) that rounding is explicit (rbf); otherwise the pack below IS that rounding — rounding twice to the same grid
-// changes nothing, and leaving the first one out saves ~10 VALU instructions per 4 outputs (half of the epilogue's VALU work).
-template <int EPI>
-__device__ __forceinline__ float gf_epi_act(float lin) {
-    if constexpr (EPI == GF_EPI_BIAS_GELU_TANH) return gelu_tanh_f(rbf(lin));
-    else if constexpr (EPI == GF_EPI_BIAS_SILU) {
-        const float y = rbf(lin);
-        return y / (1.0f + expf(-y));
-    } else return lin;
-}
 
 // The fp8 GEMM of the small shapes (M < 512): A/W are OCP e4m3 bytes, K-step 128 elements = one 128-byte LDS row, each lane's
 // fragment is 32 consecutive k (two 16-byte chunks) and the product runs on v_mfma_scale_f32_16x16x128_f8f6f4 with unit
@@ -981,6 +970,36 @@ const u16* conv_zero_page() {
     return e == hipSuccess ? page[dev] : nullptr;
 }
 
+// The one place a GemmArgs is filled from operands and sizes: C[M, N] = A[M, K] W[N, K]^T on 256 x 256 tiles, every row of W present,
+// the K loop rotated by column tile.  What an entry point has of its own (batch strides, narrower tiles, no rotation, the rotation by
+// row tile, the convolution's geometry) it sets on the result.
+GemmArgs gemm_args(const void* A, int64_t lda, const void* W, int64_t ldw, const float* row_scale, const void* bias, void* C, int64_t ldc,
+                   const void* resid, int64_t ldr, const void* gate, int64_t M, int64_t N, int64_t K) {
+    GemmArgs a;
+    a.A = (const u16*)A;
+    a.W = (const u16*)W;
+    a.bias = (const u16*)bias;
+    a.C = (u16*)C;
+    a.R = (const u16*)resid;
+    a.gate = (const u16*)gate;
+    a.row_scale = row_scale;
+    a.M = (int)M;
+    a.N = (int)N;
+    a.K = (int)K;
+    a.lda = lda;
+    a.ldw = ldw;
+    a.ldc = ldc;
+    a.ldr = ldr;
+    a.tiles_m = (int)((M + BM - 1) / BM);
+    a.tiles_n = (int)((N + BN - 1) / BN);
+    // K tiles between the K-loop starts of neighbouring column tiles (0 = off).  The rotation changes the ORDER of the sum over k
+    // (not the sum): a4 outputs match the unrotated kernels (M < 512: the 8-wave path) to fp32 rounding, not bit for bit.
+    a.stagger = gf_options().a4_stagger.load(std::memory_order_relaxed);
+    a.wrows = (int)N;
+    a.stagger_rows = 0;
+    return a;
+}
+
 }  // namespace
 
 static int gemm_dispatch(bool fp8, const void* A, int64_t lda, const void* W, int64_t ldw, const float* row_scale,
@@ -1004,42 +1023,15 @@ static int gemm_dispatch(bool fp8, const void* A, int64_t lda, const void* W, in
     GF_CHECK_ARG(epilogue != GF_EPI_BIAS_GATE_RESID || (gate && gf_aligned16(gate)),
                  "%s: gate epilogue needs an aligned gate vector", fn);
     if (M == 0) return GF_OK;
-    GemmArgs a;
-    a.A = (const u16*)A;
-    a.W = (const u16*)W;
-    a.bias = (const u16*)bias;
-    a.C = (u16*)C;
-    a.R = (const u16*)resid;
-    a.gate = (const u16*)gate;
-    a.row_scale = row_scale;
-    a.M = (int)M;
-    a.N = (int)N;
-    a.K = (int)K;
-    a.lda = lda;
-    a.ldw = ldw;
-    a.ldc = ldc;
-    a.ldr = ldr;
-    a.tiles_m = (int)((M + BM - 1) / BM);
-    a.tiles_n = (int)((N + BN - 1) / BN);
-    // K tiles between the K-loop starts of neighbouring column tiles (0 = off).  The rotation changes the ORDER of the sum over k
-    // (not the sum): a4 outputs match the unrotated kernels (M < 512: the 8-wave path) to fp32 rounding, not bit for bit.
-    a.stagger = gf_options().a4_stagger.load(std::memory_order_relaxed);
-    a.wrows = (int)N;
-    a.stagger_rows = 0;
+    // after the zero-size return: an empty product has always been accepted whatever its epilogue
+    GF_CHECK_ARG(epilogue >= GF_EPI_BIAS && epilogue <= GF_EPI_BIAS_MUL, "%s: unknown epilogue %d", fn, epilogue);
+    const GemmArgs a = gemm_args(A, lda, W, ldw, row_scale, bias, C, ldc, resid, ldr, gate, M, N, K);
     hipStream_t s = (hipStream_t)stream;
-#define GF_GEMM_CASE(E) case E: return fp8 ? launch_gemm<E, true>(a, s) : launch_gemm<E, false>(a, s);
-    switch (epilogue) {
-        GF_GEMM_CASE(GF_EPI_BIAS)
-        GF_GEMM_CASE(GF_EPI_BIAS_GELU_TANH)
-        GF_GEMM_CASE(GF_EPI_BIAS_GATE_RESID)
-        GF_GEMM_CASE(GF_EPI_BIAS_RESID)
-        GF_GEMM_CASE(GF_EPI_BIAS_SILU)
-        GF_GEMM_CASE(GF_EPI_BIAS_MUL)
-        default:
-            gf_set_error("%s: unknown epilogue %d", fn, epilogue);
-            return GF_ERR_INVALID_ARG;
-    }
-#undef GF_GEMM_CASE
+    return gf_dispatch<GF_EPI_BIAS, GF_EPI_BIAS_GELU_TANH, GF_EPI_BIAS_GATE_RESID, GF_EPI_BIAS_RESID, GF_EPI_BIAS_SILU, GF_EPI_BIAS_MUL>(
+        epilogue, [&](auto e) {
+            constexpr int E = decltype(e)::value;
+            return fp8 ? launch_gemm<E, true>(a, s) : launch_gemm<E, false>(a, s);
+        });
 }
 
 extern "C" GF_API int gf_gemm_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, const void* bias, void* C,
@@ -1060,36 +1052,28 @@ extern "C" GF_API int gf_gemm_fp8(const void* A8, int64_t lda, const void* W8, i
 // K-loop rotation taken from the row tile (so every element sums its products in the order gf_gemm_bf16(x, w) uses) and the
 // key permutation applied where the epilogue reads its LDS image: bit-identical to gf_gemm_bf16 + gf_transpose_v32, one
 // kernel and one 2 x 335 MB pass over V less per attention.
-extern "C" GF_API int gf_linear_vt32(const void* x, int64_t ldx, const void* w, int64_t ldw, const void* bias, void* vt,
-                                     int64_t kv_len, int64_t kv_pad, int64_t N, int64_t K, void* stream) {
-    GF_CHECK_ARG(x && w && vt, "gf_linear_vt32: null x/w/vt");
-    GF_CHECK_ARG(kv_len > 0 && kv_pad >= kv_len && kv_pad % 64 == 0 && kv_pad - kv_len < 64, "gf_linear_vt32: kv_pad = kv_len rounded up to 64");
-    GF_CHECK_ARG(N >= 512 && N % 128 == 0 && K > 0 && K % 64 == 0, "gf_linear_vt32: N=%ld (>= 512, multiple of 128), K=%ld (multiple of 64)", (long)N, (long)K);
-    GF_CHECK_ARG(ldx % 8 == 0 && ldw % 8 == 0 && ldx >= K && ldw >= K, "gf_linear_vt32: leading dimensions must be multiples of 8 covering K");
-    GF_CHECK_ARG(gf_aligned16(x) && gf_aligned16(w) && gf_aligned16(vt) && (!bias || ((uintptr_t)bias & 1u) == 0), "gf_linear_vt32: alignment");
-    GF_CHECK_ARG(N * kv_pad < (1LL << 31) && 256L * ldx * 2 + K * 2L < (1L << 31) && 256L * ldw * 2 + K * 2L < (1L << 31),
-                 "gf_linear_vt32: operand too large for 32-bit staging offsets");
-    GemmArgs a;
-    a.A = (const u16*)w;
-    a.W = (const u16*)x;
-    a.bias = (const u16*)bias;
-    a.C = (u16*)vt;
-    a.R = nullptr;
-    a.gate = nullptr;
-    a.row_scale = nullptr;
-    a.M = (int)N;
-    a.N = (int)kv_pad;
-    a.K = (int)K;
-    a.lda = ldw;
-    a.ldw = ldx;
-    a.ldc = kv_pad;
-    a.ldr = 0;
-    a.tiles_m = (int)((N + BM - 1) / BM);
-    a.tiles_n = (int)((kv_pad + BN - 1) / BN);
-    a.stagger = gf_options().a4_stagger.load(std::memory_order_relaxed);
+static int linear_vt32_impl(bool fp8, const void* x, int64_t ldx, const float* x_scale, const void* w, int64_t ldw, const void* bias, void* vt,
+                            int64_t kv_len, int64_t kv_pad, int64_t N, int64_t K, void* stream) {
+    const char* fn = fp8 ? "gf_linear_vt32_fp8" : "gf_linear_vt32";
+    const int bke = fp8 ? 128 : 64, lal = fp8 ? 16 : 8, esz = fp8 ? 1 : 2;
+    GF_CHECK_ARG(x && w && vt && (!fp8 || x_scale), "%s: null %s", fn, fp8 ? "x8/w8/vt/x_scale" : "x/w/vt");
+    GF_CHECK_ARG(kv_len > 0 && kv_pad >= kv_len && kv_pad % 64 == 0 && kv_pad - kv_len < 64, "%s: kv_pad = kv_len rounded up to 64", fn);
+    GF_CHECK_ARG(N >= 512 && N % 128 == 0 && K > 0 && K % bke == 0, "%s: N=%ld (>= 512, multiple of 128), K=%ld (multiple of %d)", fn, (long)N,
+                 (long)K, bke);
+    GF_CHECK_ARG(ldx % lal == 0 && ldw % lal == 0 && ldx >= K && ldw >= K, "%s: leading dimensions must be multiples of %d covering K", fn, lal);
+    GF_CHECK_ARG(gf_aligned16(x) && gf_aligned16(w) && gf_aligned16(vt) && (!bias || ((uintptr_t)bias & 1u) == 0), "%s: alignment", fn);
+    GF_CHECK_ARG(N * kv_pad < (1LL << 31) && (256L * ldx + K) * esz < (1L << 31) && (256L * ldw + K) * esz < (1L << 31),
+                 "%s: operand too large for 32-bit staging offsets", fn);
+    // the operands swapped: A := w, W := x, C = w x^T is V^T row-major; the key columns from kv_len to kv_pad do not exist
+    GemmArgs a = gemm_args(w, ldw, x, ldx, x_scale, bias, vt, kv_pad, nullptr, 0, nullptr, N, kv_pad, K);
     a.wrows = (int)kv_len;
     a.stagger_rows = 1;
-    return launch_gemm_a4<GF_EPI_VT32>(a, (hipStream_t)stream);
+    return fp8 ? launch_gemm_a4<GF_EPI_VT32, true>(a, (hipStream_t)stream) : launch_gemm_a4<GF_EPI_VT32>(a, (hipStream_t)stream);
+}
+
+extern "C" GF_API int gf_linear_vt32(const void* x, int64_t ldx, const void* w, int64_t ldw, const void* bias, void* vt,
+                                     int64_t kv_len, int64_t kv_pad, int64_t N, int64_t K, void* stream) {
+    return linear_vt32_impl(false, x, ldx, nullptr, w, ldw, bias, vt, kv_len, kv_pad, N, K, stream);
 }
 
 // gf_linear_vt32 on the fp8_linear contract (BASELINE config 5): x8 / w8 are e4m3 bytes, x_scale the tokens' activation scales
@@ -1098,34 +1082,7 @@ extern "C" GF_API int gf_linear_vt32(const void* x, int64_t ldx, const void* w, 
 // row tile).
 extern "C" GF_API int gf_linear_vt32_fp8(const void* x8, int64_t ldx, const float* x_scale, const void* w8, int64_t ldw, const void* bias,
                                          void* vt, int64_t kv_len, int64_t kv_pad, int64_t N, int64_t K, void* stream) {
-    GF_CHECK_ARG(x8 && w8 && vt && x_scale, "gf_linear_vt32_fp8: null x8/w8/vt/x_scale");
-    GF_CHECK_ARG(kv_len > 0 && kv_pad >= kv_len && kv_pad % 64 == 0 && kv_pad - kv_len < 64, "gf_linear_vt32_fp8: kv_pad = kv_len rounded up to 64");
-    GF_CHECK_ARG(N >= 512 && N % 128 == 0 && K > 0 && K % 128 == 0, "gf_linear_vt32_fp8: N=%ld (>= 512, multiple of 128), K=%ld (multiple of 128)", (long)N, (long)K);
-    GF_CHECK_ARG(ldx % 16 == 0 && ldw % 16 == 0 && ldx >= K && ldw >= K, "gf_linear_vt32_fp8: leading dimensions must be multiples of 16 covering K");
-    GF_CHECK_ARG(gf_aligned16(x8) && gf_aligned16(w8) && gf_aligned16(vt) && (!bias || ((uintptr_t)bias & 1u) == 0), "gf_linear_vt32_fp8: alignment");
-    GF_CHECK_ARG(N * kv_pad < (1LL << 31) && 256L * ldx + K < (1L << 31) && 256L * ldw + K < (1L << 31),
-                 "gf_linear_vt32_fp8: operand too large for 32-bit staging offsets");
-    GemmArgs a;
-    a.A = (const u16*)w8;
-    a.W = (const u16*)x8;
-    a.bias = (const u16*)bias;
-    a.C = (u16*)vt;
-    a.R = nullptr;
-    a.gate = nullptr;
-    a.row_scale = x_scale;
-    a.M = (int)N;
-    a.N = (int)kv_pad;
-    a.K = (int)K;
-    a.lda = ldw;
-    a.ldw = ldx;
-    a.ldc = kv_pad;
-    a.ldr = 0;
-    a.tiles_m = (int)((N + BM - 1) / BM);
-    a.tiles_n = (int)((kv_pad + BN - 1) / BN);
-    a.stagger = gf_options().a4_stagger.load(std::memory_order_relaxed);
-    a.wrows = (int)kv_len;
-    a.stagger_rows = 1;
-    return launch_gemm_a4<GF_EPI_VT32, true>(a, (hipStream_t)stream);
+    return linear_vt32_impl(true, x8, ldx, x_scale, w8, ldw, bias, vt, kv_len, kv_pad, N, K, stream);
 }
 
 // `batch` independent products C_b = A_b W_b^T (no bias, no epilogue) in ONE launch: problem b reads A + b strideA, W + b strideW and
@@ -1145,32 +1102,13 @@ extern "C" GF_API int gf_gemm_bf16_batched(const void* A, int64_t lda, int64_t s
                  "gf_gemm_bf16_batched: leading dimensions / strides must be multiples of 8 elements covering K / N");
     GF_CHECK_ARG(gf_aligned16(A) && gf_aligned16(W) && gf_aligned16(C), "gf_gemm_bf16_batched: 16-byte alignment required");
     GF_CHECK_ARG(M < (1L << 30) && N < (1L << 30), "gf_gemm_bf16_batched: M / N too large");
-    GemmArgs a;
-    a.A = (const u16*)A;
-    a.W = (const u16*)W;
-    a.bias = nullptr;
-    a.C = (u16*)C;
-    a.R = nullptr;
-    a.gate = nullptr;
-    a.row_scale = nullptr;
-    a.M = (int)M;
-    a.N = (int)N;
-    a.K = (int)K;
-    a.lda = lda;
-    a.ldw = ldw;
-    a.ldc = ldc;
-    a.ldr = 0;
+    GemmArgs a = gemm_args(A, lda, W, ldw, nullptr, nullptr, C, ldc, nullptr, 0, nullptr, M, N, K);
     a.sA = strideA;
     a.sW = strideW;
     a.sC = strideC;
     const bool narrow = N <= 128;
-    a.tiles_m = (int)((M + BM - 1) / BM);
-    a.tiles_n = narrow ? (int)((N + 127) / 128) : (int)((N + BN - 1) / BN);
+    if (narrow) a.tiles_n = (int)((N + 127) / 128);
     a.stagger = 0;
-    a.wrows = (int)N;
-    a.stagger_rows = 0;
-    a.group_m = 0;
-    a.cv = ConvGeom{};
     return narrow ? launch_conv<GF_EPI_BIAS, 1, 0>(a, (hipStream_t)stream, (int)batch) : launch_conv<GF_EPI_BIAS, 2, 0>(a, (hipStream_t)stream, (int)batch);
 }
 
@@ -1205,31 +1143,15 @@ extern "C" GF_API int gf_conv3d_bf16(const void* src, const void* cache, const v
     const long M = T_out * Ho * Wo;
     GF_CHECK_ARG(M < (1L << 30), "gf_conv3d_bf16: too many output pixels");
     if (M == 0) return GF_OK;
-    GemmArgs a;
-    a.A = nullptr;
-    a.W = (const u16*)Wm;
-    a.bias = (const u16*)bias;
-    a.C = (u16*)out;
-    a.R = (const u16*)resid;
-    a.gate = nullptr;
-    a.row_scale = nullptr;
-    a.M = (int)M;
-    a.N = (int)N;
-    a.K = (int)K;
-    a.lda = 0;
-    a.ldw = ldw;
-    a.ldc = ldc;
-    a.ldr = ldr;
+    GemmArgs a = gemm_args(nullptr, 0, Wm, ldw, nullptr, bias, out, ldc, resid, ldr, nullptr, M, N, K);
     // Cout <= 128 (the 96-channel level, the RGB head): the 256 x 128 tile; GF_CONV_NB=2 forces the 256 x 256 tile (A/B timing)
     const int force_nb = gf_options().conv_nb.load(std::memory_order_relaxed);
     const bool narrow = force_nb ? force_nb == 1 : N <= 128;
     // 192-wide tiles where they cover N with fewer padded columns than 256-wide ones (Cout = 192, 384: none instead of a quarter)
     const bool w192 = !narrow && !force_nb && ((N + 191) / 192) * 192 < ((N + BN - 1) / BN) * BN;
-    a.tiles_m = (int)((M + BM - 1) / BM);
-    a.tiles_n = narrow ? (int)((N + 127) / 128) : (w192 ? (int)((N + 191) / 192) : (int)((N + BN - 1) / BN));
+    if (narrow) a.tiles_n = (int)((N + 127) / 128);
+    else if (w192) a.tiles_n = (int)((N + 191) / 192);
     a.stagger = 0;
-    a.wrows = (int)N;
-    a.stagger_rows = 0;
     a.cv.src = (const u16*)src;
     a.cv.cache = (const u16*)cache;
     a.cv.zero = conv_zero_page();
@@ -1272,14 +1194,12 @@ extern "C" GF_API int gf_conv3d_bf16(const void* src, const void* cache, const v
     // contiguous source frames and stride-1 taps: the pointer-per-row gather (GF_CONV_GATHER=1 forces the general one, A/B)
     const int force_g = gf_options().conv_gather.load(std::memory_order_relaxed);
     const bool fast = force_g != 1 && mode == 0 && (kt == 1 || !cache);
-#define GF_CONV_CASE(E, NBV, CV) return launch_conv<E, NBV, CV>(a, s)
-    if (fast) {
-        if (narrow) { if (epilogue == GF_EPI_BIAS) GF_CONV_CASE(GF_EPI_BIAS, 1, 2); else GF_CONV_CASE(GF_EPI_BIAS_RESID, 1, 2); }
-        if (w192) { if (epilogue == GF_EPI_BIAS) GF_CONV_CASE(GF_EPI_BIAS, 3, 2); else GF_CONV_CASE(GF_EPI_BIAS_RESID, 3, 2); }
-        if (epilogue == GF_EPI_BIAS) GF_CONV_CASE(GF_EPI_BIAS, 2, 2); else GF_CONV_CASE(GF_EPI_BIAS_RESID, 2, 2);
-    }
-    if (narrow) { if (epilogue == GF_EPI_BIAS) GF_CONV_CASE(GF_EPI_BIAS, 1, 1); else GF_CONV_CASE(GF_EPI_BIAS_RESID, 1, 1); }
-    if (w192) { if (epilogue == GF_EPI_BIAS) GF_CONV_CASE(GF_EPI_BIAS, 3, 1); else GF_CONV_CASE(GF_EPI_BIAS_RESID, 3, 1); }
-    if (epilogue == GF_EPI_BIAS) GF_CONV_CASE(GF_EPI_BIAS, 2, 1); else GF_CONV_CASE(GF_EPI_BIAS_RESID, 2, 1);
-#undef GF_CONV_CASE
+    // (EPI, NB, CONV) of gemm_ph_kernel: narrow before w192 before the 256-wide tile
+    return gf_dispatch<GF_EPI_BIAS, GF_EPI_BIAS_RESID>(epilogue, [&](auto e) {
+        return gf_dispatch<1, 3, 2>(narrow ? 1 : (w192 ? 3 : 2), [&](auto nb) {
+            return gf_dispatch<2, 1>(fast ? 2 : 1, [&](auto cv) {
+                return launch_conv<decltype(e)::value, decltype(nb)::value, decltype(cv)::value>(a, s);
+            });
+        });
+    });
 }

@@ -35,32 +35,22 @@ constexpr int GROUP_M = 8;
 typedef __attribute__((ext_vector_type(8))) int i32x8;
 
 struct Fp4Args {
-    const char* A;
-    const char* W;
-    const unsigned char* sa;
-    const unsigned char* sw;
-    const u16* bias;
-    u16* C;
-    const u16* R;
-    const u16* gate;
-    int M, N, K;
-    long lda, ldw, lsa, lsw, ldc, ldr;
-    int tiles_m, tiles_n;
+    const char* A = nullptr;
+    const char* W = nullptr;
+    const unsigned char* sa = nullptr;
+    const unsigned char* sw = nullptr;
+    const u16* bias = nullptr;
+    u16* C = nullptr;
+    const u16* R = nullptr;
+    const u16* gate = nullptr;
+    int M = 0, N = 0, K = 0;
+    long lda = 0, ldw = 0, lsa = 0, lsw = 0, ldc = 0, ldr = 0;
+    int tiles_m = 0, tiles_n = 0;
     // Q4 (gf_gemm_mxfp4_q4): the output as the next GEMM's A operand instead of C — packed codes [M, N/2] and scales [M, N/32], strides in bytes
-    unsigned char* C4;
-    unsigned char* sc;
-    long ldc4, lsc;
+    unsigned char* C4 = nullptr;
+    unsigned char* sc = nullptr;
+    long ldc4 = 0, lsc = 0;
 };
-
-// the Linear's own output is rounded to bf16 before an activation is applied to it: the expression of gf_gemm.hip's epilogues
-template <int EPI>
-__device__ __forceinline__ float fp4_epi_act(float lin) {
-    if constexpr (EPI == GF_EPI_BIAS_GELU_TANH) return gelu_tanh_f(rbf(lin));
-    else if constexpr (EPI == GF_EPI_BIAS_SILU) {
-        const float y = rbf(lin);
-        return y / (1.0f + expf(-y));
-    } else return lin;
-}
 
 // Q4: the finished bf16 output is quantised to MXFP4 in the read-back loop (gf_mxfp4_quant.h) and only its codes and scales are stored:
 // a lane of that loop holds 8 consecutive columns of one row and lanes cc = 0..3 / 4..7 are the two 32-aligned MX blocks of the wave's
@@ -227,7 +217,7 @@ __global__ __launch_bounds__(FP4_THREADS, 2) void gemm_mxfp4_kernel(const Fp4Arg
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const bool is_nan = row_nan || ((nan_col[j] >> (8 * r)) & 1u);
-                    y[r] = fp4_epi_act<EPI>(is_nan ? qnan : acc[i][j][r] + bv[r]);
+                    y[r] = gf_epi_act<EPI>(is_nan ? qnan : acc[i][j][r] + bv[r]);
                 }
                 u32x2 pk;
                 pk[0] = pack2bf(y[0], y[1]);
@@ -295,16 +285,54 @@ __global__ __launch_bounds__(256) void quant_mxfp4_kernel(const u16* __restrict_
     }
 }
 
-template <int EPI>
-int launch_mxfp4(const Fp4Args& a, hipStream_t stream) {
-    return gf_launch_lds<gemm_mxfp4_kernel<EPI>>("gf_gemm_mxfp4", GF_ATTR_MSG_BYTES, "gf_gemm_mxfp4", dim3((unsigned)(a.tiles_m * a.tiles_n)),
-                                                  dim3(FP4_THREADS), FP4_LDS, stream, a);
+template <int EPI, bool Q4>
+int launch_mxfp4(const char* fn, const Fp4Args& a, hipStream_t stream) {
+    return gf_launch_lds<gemm_mxfp4_kernel<EPI, Q4>>(fn, GF_ATTR_MSG_BYTES, fn, dim3((unsigned)(a.tiles_m * a.tiles_n)), dim3(FP4_THREADS),
+                                                      FP4_LDS, stream, a);
 }
 
-template <int EPI>
-int launch_mxfp4_q4(const Fp4Args& a, hipStream_t stream) {
-    return gf_launch_lds<gemm_mxfp4_kernel<EPI, true>>("gf_gemm_mxfp4_q4", GF_ATTR_MSG_BYTES, "gf_gemm_mxfp4_q4",
-                                                        dim3((unsigned)(a.tiles_m * a.tiles_n)), dim3(FP4_THREADS), FP4_LDS, stream, a);
+// The operand rules gf_gemm_mxfp4 and gf_gemm_mxfp4_q4 share, in the order both have always answered in.  The output is the one operand
+// that differs (q4: packed codes C4 [M, N/2] with ldo in bytes and scales c_scale [M, N/32]; else bf16 C [M, N] with ldo in elements), and
+// its rules sit between the shared ones, so they are stated here too; what follows the operands (resid / gate, the epilogue) is the caller's.
+int mxfp4_check(const char* fn, bool q4, const void* A4, int64_t lda, const void* a_scale, int64_t a_scale_stride, const void* W4, int64_t ldw,
+                const void* w_scale, int64_t w_scale_stride, const void* bias, const void* out, int64_t ldo, const void* c_scale,
+                int64_t c_scale_stride, int64_t M, int64_t N, int64_t K) {
+    GF_CHECK_ARG(A4 && W4 && out && (!q4 || c_scale) && a_scale && w_scale, "%s: null A/W/C/scales", fn);
+    GF_CHECK_ARG(M >= 0 && N > 0 && K > 0, "%s: bad sizes M=%ld N=%ld K=%ld", fn, (long)M, (long)N, (long)K);
+    GF_CHECK_ARG(K % 256 == 0, "%s: K=%ld must be a multiple of %d", fn, (long)K, 256);
+    GF_CHECK_ARG(N % (q4 ? 32 : 8) == 0, "%s: N=%ld must be a multiple of %s", fn, (long)N, q4 ? "32 (one E8M0 scale per 32 output columns)" : "8");
+    GF_CHECK_ARG(lda % 16 == 0 && ldw % 16 == 0 && lda >= K / 2 && ldw >= K / 2 && (q4 ? ldo % 16 == 0 && ldo >= N / 2 : ldo % 8 == 0 && ldo >= N),
+                 "%s: leading dimensions must be multiples of %d %s and cover the row", fn, 16, q4 ? "(A/W/C4, in bytes)" : "(A/W) / 8 (C)");
+    GF_CHECK_ARG(a_scale_stride >= K / 32 && w_scale_stride >= K / 32, "%s: scale strides must cover K/32 = %ld blocks", fn, (long)(K / 32));
+    GF_CHECK_ARG(!q4 || c_scale_stride >= N / 32, "%s: c_scale_stride must cover N/32 = %ld blocks", fn, (long)(N / 32));
+    GF_CHECK_ARG(gf_aligned16(A4) && gf_aligned16(W4) && gf_aligned16(out) && (!bias || gf_aligned16(bias)),
+                 "%s: 16-byte alignment required", fn);
+    GF_CHECK_ARG(M < (1 << 30) && N < (1 << 30), "%s: M/N too large", fn);
+    GF_CHECK_ARG(256L * lda + K / 2 < (1L << 31) && 256L * ldw + K / 2 < (1L << 31) && 256L * a_scale_stride + K / 32 < (1L << 31) &&
+                     256L * w_scale_stride + K / 32 < (1L << 31),
+                 "%s: operand too large for 32-bit staging offsets", fn);
+    return GF_OK;
+}
+
+// The one place an Fp4Args is filled: the operands both entries share; the output (C / R / gate, or C4 / sc) is set by the caller.
+Fp4Args mxfp4_args(const void* A4, int64_t lda, const void* a_scale, int64_t a_scale_stride, const void* W4, int64_t ldw, const void* w_scale,
+                   int64_t w_scale_stride, const void* bias, int64_t M, int64_t N, int64_t K) {
+    Fp4Args a;
+    a.A = (const char*)A4;
+    a.W = (const char*)W4;
+    a.sa = (const unsigned char*)a_scale;
+    a.sw = (const unsigned char*)w_scale;
+    a.bias = (const u16*)bias;
+    a.M = (int)M;
+    a.N = (int)N;
+    a.K = (int)K;
+    a.lda = lda;
+    a.ldw = ldw;
+    a.lsa = a_scale_stride;
+    a.lsw = w_scale_stride;
+    a.tiles_m = (int)((M + BM - 1) / BM);
+    a.tiles_n = (int)((N + BN - 1) / BN);
+    return a;
 }
 
 }  // namespace
@@ -330,19 +358,8 @@ extern "C" GF_API int gf_gemm_mxfp4(const void* A4, int64_t lda, const void* a_s
                                     const void* w_scale, int64_t w_scale_stride, const void* bias, void* C, int64_t ldc, int64_t M,
                                     int64_t N, int64_t K, int epilogue, const void* resid, int64_t ldr, const void* gate, void* stream) {
     const char* fn = "gf_gemm_mxfp4";
-    GF_CHECK_ARG(A4 && W4 && C && a_scale && w_scale, "%s: null A/W/C/scales", fn);
-    GF_CHECK_ARG(M >= 0 && N > 0 && K > 0, "%s: bad sizes M=%ld N=%ld K=%ld", fn, (long)M, (long)N, (long)K);
-    GF_CHECK_ARG(K % 256 == 0, "%s: K=%ld must be a multiple of %d", fn, (long)K, 256);
-    GF_CHECK_ARG(N % 8 == 0, "%s: N=%ld must be a multiple of 8", fn, (long)N);
-    GF_CHECK_ARG(lda % 16 == 0 && ldw % 16 == 0 && ldc % 8 == 0 && lda >= K / 2 && ldw >= K / 2 && ldc >= N,
-                 "%s: leading dimensions must be multiples of %d (A/W) / 8 (C) and cover the row", fn, 16);
-    GF_CHECK_ARG(a_scale_stride >= K / 32 && w_scale_stride >= K / 32, "%s: scale strides must cover K/32 = %ld blocks", fn, (long)(K / 32));
-    GF_CHECK_ARG(gf_aligned16(A4) && gf_aligned16(W4) && gf_aligned16(C) && (!bias || gf_aligned16(bias)),
-                 "%s: 16-byte alignment required", fn);
-    GF_CHECK_ARG(M < (1 << 30) && N < (1 << 30), "%s: M/N too large", fn);
-    GF_CHECK_ARG(256L * lda + K / 2 < (1L << 31) && 256L * ldw + K / 2 < (1L << 31) && 256L * a_scale_stride + K / 32 < (1L << 31) &&
-                     256L * w_scale_stride + K / 32 < (1L << 31),
-                 "%s: operand too large for 32-bit staging offsets", fn);
+    if (const int rc = mxfp4_check(fn, false, A4, lda, a_scale, a_scale_stride, W4, ldw, w_scale, w_scale_stride, bias, C, ldc, nullptr, 0, M, N, K))
+        return rc;
     const bool need_r = epilogue == GF_EPI_BIAS_GATE_RESID || epilogue == GF_EPI_BIAS_RESID || epilogue == GF_EPI_BIAS_MUL;
     GF_CHECK_ARG(!need_r || (resid && ldr % 8 == 0 && ldr >= N && gf_aligned16(resid)),
                  "%s: residual epilogue needs an aligned resid with ldr >= N", fn);
@@ -350,90 +367,33 @@ extern "C" GF_API int gf_gemm_mxfp4(const void* A4, int64_t lda, const void* a_s
                  "%s: gate epilogue needs an aligned gate vector", fn);
     GF_CHECK_ARG(epilogue >= GF_EPI_BIAS && epilogue <= GF_EPI_BIAS_MUL, "%s: unknown epilogue %d", fn, epilogue);
     if (M == 0) return GF_OK;
-    Fp4Args a;
-    a.A = (const char*)A4;
-    a.W = (const char*)W4;
-    a.sa = (const unsigned char*)a_scale;
-    a.sw = (const unsigned char*)w_scale;
-    a.bias = (const u16*)bias;
+    Fp4Args a = mxfp4_args(A4, lda, a_scale, a_scale_stride, W4, ldw, w_scale, w_scale_stride, bias, M, N, K);
     a.C = (u16*)C;
     a.R = (const u16*)resid;
     a.gate = (const u16*)gate;
-    a.M = (int)M;
-    a.N = (int)N;
-    a.K = (int)K;
-    a.lda = lda;
-    a.ldw = ldw;
-    a.lsa = a_scale_stride;
-    a.lsw = w_scale_stride;
     a.ldc = ldc;
     a.ldr = ldr;
-    a.C4 = a.sc = nullptr;
-    a.ldc4 = a.lsc = 0;
-    a.tiles_m = (int)((M + BM - 1) / BM);
-    a.tiles_n = (int)((N + BN - 1) / BN);
-    hipStream_t s = (hipStream_t)stream;
-    switch (epilogue) {
-        case GF_EPI_BIAS: return launch_mxfp4<GF_EPI_BIAS>(a, s);
-        case GF_EPI_BIAS_GELU_TANH: return launch_mxfp4<GF_EPI_BIAS_GELU_TANH>(a, s);
-        case GF_EPI_BIAS_GATE_RESID: return launch_mxfp4<GF_EPI_BIAS_GATE_RESID>(a, s);
-        case GF_EPI_BIAS_RESID: return launch_mxfp4<GF_EPI_BIAS_RESID>(a, s);
-        case GF_EPI_BIAS_SILU: return launch_mxfp4<GF_EPI_BIAS_SILU>(a, s);
-        default: return launch_mxfp4<GF_EPI_BIAS_MUL>(a, s);
-    }
+    return gf_dispatch<GF_EPI_BIAS, GF_EPI_BIAS_GELU_TANH, GF_EPI_BIAS_GATE_RESID, GF_EPI_BIAS_RESID, GF_EPI_BIAS_SILU, GF_EPI_BIAS_MUL>(
+        epilogue, [&](auto e) { return launch_mxfp4<decltype(e)::value, false>(fn, a, (hipStream_t)stream); });
 }
 
 extern "C" GF_API int gf_gemm_mxfp4_q4(const void* A4, int64_t lda, const void* a_scale, int64_t a_scale_stride, const void* W4, int64_t ldw,
                                        const void* w_scale, int64_t w_scale_stride, const void* bias, void* C4, int64_t ldc4, void* c_scale,
                                        int64_t c_scale_stride, int64_t M, int64_t N, int64_t K, int epilogue, void* stream) {
     const char* fn = "gf_gemm_mxfp4_q4";
-    GF_CHECK_ARG(A4 && W4 && C4 && c_scale && a_scale && w_scale, "%s: null A/W/C/scales", fn);
-    GF_CHECK_ARG(M >= 0 && N > 0 && K > 0, "%s: bad sizes M=%ld N=%ld K=%ld", fn, (long)M, (long)N, (long)K);
-    GF_CHECK_ARG(K % 256 == 0, "%s: K=%ld must be a multiple of %d", fn, (long)K, 256);
-    GF_CHECK_ARG(N % 32 == 0, "%s: N=%ld must be a multiple of 32 (one E8M0 scale per 32 output columns)", fn, (long)N);
-    GF_CHECK_ARG(lda % 16 == 0 && ldw % 16 == 0 && ldc4 % 16 == 0 && lda >= K / 2 && ldw >= K / 2 && ldc4 >= N / 2,
-                 "%s: leading dimensions must be multiples of %d (A/W/C4, in bytes) and cover the row", fn, 16);
-    GF_CHECK_ARG(a_scale_stride >= K / 32 && w_scale_stride >= K / 32, "%s: scale strides must cover K/32 = %ld blocks", fn, (long)(K / 32));
-    GF_CHECK_ARG(c_scale_stride >= N / 32, "%s: c_scale_stride must cover N/32 = %ld blocks", fn, (long)(N / 32));
-    GF_CHECK_ARG(gf_aligned16(A4) && gf_aligned16(W4) && gf_aligned16(C4) && (!bias || gf_aligned16(bias)),
-                 "%s: 16-byte alignment required", fn);
-    GF_CHECK_ARG(M < (1 << 30) && N < (1 << 30), "%s: M/N too large", fn);
-    GF_CHECK_ARG(256L * lda + K / 2 < (1L << 31) && 256L * ldw + K / 2 < (1L << 31) && 256L * a_scale_stride + K / 32 < (1L << 31) &&
-                     256L * w_scale_stride + K / 32 < (1L << 31),
-                 "%s: operand too large for 32-bit staging offsets", fn);
+    if (const int rc = mxfp4_check(fn, true, A4, lda, a_scale, a_scale_stride, W4, ldw, w_scale, w_scale_stride, bias, C4, ldc4, c_scale,
+                                   c_scale_stride, M, N, K))
+        return rc;
     GF_CHECK_ARG(epilogue >= GF_EPI_BIAS && epilogue <= GF_EPI_BIAS_MUL, "%s: unknown epilogue %d", fn, epilogue);
     GF_CHECK_ARG(epilogue == GF_EPI_BIAS || epilogue == GF_EPI_BIAS_GELU_TANH || epilogue == GF_EPI_BIAS_SILU,
                  "%s: epilogue %d takes a second operand; the quantising epilogue serves GF_EPI_BIAS, GF_EPI_BIAS_GELU_TANH and "
                  "GF_EPI_BIAS_SILU (use gf_gemm_mxfp4 + gf_quant_mxfp4)", fn, epilogue);
     if (M == 0) return GF_OK;
-    Fp4Args a;
-    a.A = (const char*)A4;
-    a.W = (const char*)W4;
-    a.sa = (const unsigned char*)a_scale;
-    a.sw = (const unsigned char*)w_scale;
-    a.bias = (const u16*)bias;
-    a.C = nullptr;
-    a.R = nullptr;
-    a.gate = nullptr;
-    a.M = (int)M;
-    a.N = (int)N;
-    a.K = (int)K;
-    a.lda = lda;
-    a.ldw = ldw;
-    a.lsa = a_scale_stride;
-    a.lsw = w_scale_stride;
-    a.ldc = 0;
-    a.ldr = 0;
-    a.tiles_m = (int)((M + BM - 1) / BM);
-    a.tiles_n = (int)((N + BN - 1) / BN);
+    Fp4Args a = mxfp4_args(A4, lda, a_scale, a_scale_stride, W4, ldw, w_scale, w_scale_stride, bias, M, N, K);
     a.C4 = (unsigned char*)C4;
     a.sc = (unsigned char*)c_scale;
     a.ldc4 = ldc4;
     a.lsc = c_scale_stride;
-    hipStream_t s = (hipStream_t)stream;
-    switch (epilogue) {
-        case GF_EPI_BIAS: return launch_mxfp4_q4<GF_EPI_BIAS>(a, s);
-        case GF_EPI_BIAS_GELU_TANH: return launch_mxfp4_q4<GF_EPI_BIAS_GELU_TANH>(a, s);
-        default: return launch_mxfp4_q4<GF_EPI_BIAS_SILU>(a, s);
-    }
+    return gf_dispatch<GF_EPI_BIAS, GF_EPI_BIAS_GELU_TANH, GF_EPI_BIAS_SILU>(
+        epilogue, [&](auto e) { return launch_mxfp4<decltype(e)::value, true>(fn, a, (hipStream_t)stream); });
 }

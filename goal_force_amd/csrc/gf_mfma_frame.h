@@ -87,3 +87,12 @@ static inline int gf_launch_lds(const char* who, GfAttrMsg msg, const char* name
     GF_CHECK_LAUNCH(name);
     return GF_OK;
 }
+
+// ---- host: from a run-time value to a template argument.  gf_dispatch<V0, V1, ...>(v, f) returns f(std::integral_constant<int, Vi>{})
+// for the Vi that equals v; the LAST value also answers every other v, like the `default:` of a switch (callers have checked v).
+// Nested calls select among a product of values; f is instantiated once per listed value and for nothing else.
+template <int V0, int... Vs, class F>
+static inline int gf_dispatch(int v, F&& f) {
+    if constexpr (sizeof...(Vs) == 0) return f(std::integral_constant<int, V0>{});
+    else return v == V0 ? f(std::integral_constant<int, V0>{}) : gf_dispatch<Vs...>(v, f);
+}
