@@ -8,7 +8,8 @@ refusal the header documents.  Exit code 1 when anything failed.  `--only fwdrow
 row kernels against the exact chains of tests/forward_refs.py, `--only attnfwd` (opt-in as well) the attention forward's entry points
 against the bounds of tests/attention_fwd_refs.py, `--only gemmpin` (opt-in) the GEMM family against the exact chain and the two bars
 of tests/gemm_refs.py, `--only vaepin` (opt-in) the VAE's convolution kernels against the plain fp64 convolution of tests/vae_refs.py
-through the same bars."""
+through the same bars, `--only crossfold` (opt-in) the folded cross-attention's two kernels through the raw C ABI against the bars of
+tests/cross_fold_refs.py."""
 import argparse
 import math
 import os
@@ -565,9 +566,74 @@ def case_vaepin(rnd, g):
     return desc + f" | {differing} elements differ", (math.inf if differing else 0.0), 1.0
 
 
+def case_crossfold(rnd, g):
+    """gf_cross_probs and gf_cross_fold_table pinned as tests/test_cross_fold_pinned_gpu.py pins them (helpers: tests/cross_fold_refs.py),
+    through the raw C ABI at a random q_len, n_keys, n_pad (minimal or above), head count, multiplicity and data class, q / k / v / w_o as
+    column slices of wider buffers, p and u with a row gap (u at a 2-byte offset).  err = the largest of P's element, last-key and
+    row-sum ratios, its differing-bit count over the cap, a non-zero pad column or a written gap (inf); the table: any differing bit on
+    the exact classes (inf), gemm_refs' two bars on gauss; bar 1."""
+    if os.path.join(ROOT, "tests") not in sys.path:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import cross_fold_refs as R
+    import gemm_refs as G
+    lib = ops._lib.load()
+    n = rnd.choice(list(R.N_KEYS) + [rnd.randrange(1, 64)])
+    n_pad = rnd.choice([p for p in (16, 32, 48, 64) if p > n][:2])
+    heads, sq = rnd.choice([1, 2, 3, 5, 8]), rnd.choice(list(R.Q_LENS) + [rnd.randrange(1, 400)])
+    cls = rnd.choice([c for c in R.CLASSES if n > 1 or not c.startswith("pad_")])
+    m = 472.0 if cls.startswith("pad_") else rnd.choice(list(R.MULTS) + [1.0 + 510.0 * rnd.random()])
+    cs = R.case(cls, sq, n, n_pad, heads, m)
+    D, W, sent = heads * R.HD, heads * n_pad, 0x5A5A
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def wide(t):                                   # a column slice of a NaN-filled parent, 16-byte aligned
+        off, extra = 8 * rnd.choice([0, 1, 2]), 8 * rnd.choice([0, 1, 3])
+        big = torch.full((t.shape[0] + 2, off + t.shape[1] + extra), float("nan"), dtype=BF, device="cuda")
+        big[:t.shape[0], off:off + t.shape[1]] = t.cuda()
+        return big[:t.shape[0], off:off + t.shape[1]]
+
+    q, k = wide(cs.q), wide(cs.k)
+    gap = 4 * rnd.choice([0, 1, 2])
+    pbuf = torch.empty((sq + 2, W + gap), dtype=BF, device="cuda")
+    pbuf.view(torch.int16).fill_(sent)
+    ops._lib.check(lib.gf_cross_probs(q.data_ptr(), k.data_ptr(), pbuf.data_ptr(), sq, n, n_pad, heads, R.HD, q.stride(0), k.stride(0), W + gap,
+                                      float(cs.scale), float(m), stream), "gf_cross_probs")
+    torch.cuda.synchronize()
+    pi = pbuf.view(torch.int16)
+    wrote = bool((pi[:sq, W:] != sent).any()) or bool((pi[sq:] != sent).any())
+    j = R.judge_probs(pbuf[:sq, :W].cpu().view(sq, heads, n_pad), cs)
+    err = max(j["elem"], j["last"], j["row"], j["differing"] / max(j["cap"], 1), 0.0 if j["zeros"] and not wrote else math.inf)
+    desc = f"crossfold {cls} q={sq} keys={n} n_pad={n_pad} heads={heads} m={m:.4g} p gap {gap} | {R.describe_probs(j)}"
+    # the table on the same key count
+    tcls, n_out = rnd.choice(R.TABLE_CLASSES), rnd.choice(list(R.N_OUT) + [rnd.randrange(1, 300)])
+    v, w = R.table_inputs(tcls, n, heads, n_out)
+    vd, wd = wide(v), wide(w)
+    ugap = rnd.choice([0, 1, 3])
+    flat = torch.empty((1 + (n_out + 1) * (W + ugap),), dtype=BF, device="cuda")
+    flat.view(torch.int16).fill_(sent)
+    u = flat[1:1 + n_out * (W + ugap)].view(n_out, W + ugap)
+    ops._lib.check(lib.gf_cross_fold_table(vd.data_ptr(), wd.data_ptr(), u.data_ptr(), n, n_pad, heads, R.HD, n_out, vd.stride(0), wd.stride(0),
+                                           W + ugap, stream), "gf_cross_fold_table")
+    torch.cuda.synchronize()
+    ui = flat.view(torch.int16)
+    wrote = int(ui[0]) != sent or bool((ui[1 + n_out * (W + ugap):] != sent).any()) or bool((u.view(torch.int16)[:, W:] != sent).any())
+    got, ref = u[:, :W].cpu(), R.table_ref(v, w, heads, n_pad)
+    desc += f" || table {tcls} n_out={n_out} u gap {ugap}"
+    if tcls == "gauss":
+        tj = G.judge(got, ref, R.HD)
+        a_err = (math.inf if tj["differing"] else 0.0) if G.SHARE_CAP * tj["numel"] < 1 else tj["share"] / G.SHARE_CAP
+        terr = max(a_err, tj["row_worst"] / tj["row_cap"], tj["col_worst"] / tj["col_cap"], tj["worst"])
+        desc += " | " + G.describe(tj)
+    else:
+        differing = int((G.bits(got) != G.bits(ref.out)).sum())
+        terr = math.inf if differing else 0.0
+        desc += f" | {differing} elements differ"
+    return desc, max(err, terr, math.inf if wrote else 0.0), 1.0
+
+
 CASES = {"gemmpin": case_gemmpin, "vaepin": case_vaepin, "gemm": case_gemm, "attn": case_attn, "rows": case_rows, "cfg": case_cfg, "attnbwd": case_attnbwd, "fp8": case_fp8,
-         "batched": case_batched, "misc": case_misc, "bwdrows": case_bwdrows, "fwdrows": case_fwdrows, "attnfwd": case_attnfwd}
-OPT_IN = ("fwdrows", "attnfwd", "gemmpin", "vaepin")       # run with --only alone (bwdrows is in the default sweep): the default sweep, and the suite's run of it, stays what it was
+         "batched": case_batched, "misc": case_misc, "bwdrows": case_bwdrows, "fwdrows": case_fwdrows, "attnfwd": case_attnfwd, "crossfold": case_crossfold}
+OPT_IN = ("fwdrows", "attnfwd", "gemmpin", "vaepin", "crossfold")       # run with --only alone (bwdrows is in the default sweep): the default sweep, and the suite's run of it, stays what it was
 
 
 def main():
