@@ -22,6 +22,8 @@
 //        jj of channel 16 db + r is the same key: gf_sage_quant_vt stores every 128-key slice in that order (position 32 g + jj).
 //   Row sums l on the matrix pipe: a ninth channel block whose A fragment is e4m3 1.0 in row 0.
 //   K~ and V^T tiles (16 KiB each) arrive by LDS-DMA into a 2-deep ring; the blockIdx map is kernel 3's XCD-aware one.
+#include <cfloat>
+
 #include "gf_mfma_frame.h"
 
 namespace {
@@ -136,8 +138,11 @@ __global__ __launch_bounds__(256) void sage_quant_rows_kernel(const u16* __restr
     if ((tid & 63) == 0) wred[tid >> 6] = m;
     __syncthreads();
     const float amax = fmaxf(fmaxf(wred[0], wred[1]), fmaxf(wred[2], wred[3]));
-    const float inv = amax > 0.f ? 127.0f / amax : 0.f;
-    if (tid == 0 && b < nblk) scale[(long)h * nblk + b] = amax / 127.0f;
+    // a block whose amax is so small that 127 / amax overflows (below ~3.7e-37): inv = FLT_MAX, scale = 2^-128 = fp32(1 / FLT_MAX)
+    // (include/goalforce.h); 0 x inf would be NaN, and fmaxf(NaN, -127) code -127
+    const bool tiny = amax > 0.f && !(127.0f / amax <= FLT_MAX);
+    const float inv = amax > 0.f ? (tiny ? FLT_MAX : 127.0f / amax) : 0.f;
+    if (tid == 0 && b < nblk) scale[(long)h * nblk + b] = tiny ? 0x1p-128f : amax / 127.0f;
 #pragma unroll
     for (int i = 0; i < PER; ++i) {
         const int ci = tid + 256 * i, row = b * BR + (ci >> 4), c8 = ci & 15;
@@ -167,8 +172,11 @@ __global__ __launch_bounds__(256) void sage_quant_vt_kernel(const u16* __restric
         double a = 0.0;
         for (int i = 0; i < nch; ++i) a = fmax(a, partial[((long)h * SAGE_NCH + i) * HD + tid]);
         const float amax = (float)a;
-        s_inv[tid] = amax > 0.f ? 448.0f / amax : 0.f;
-        if (t == 0) vscale[h * HD + tid] = amax / 448.0f;
+        // a channel whose amax is so small that 448 / amax overflows (below ~1.3e-36): inv = FLT_MAX, scale = 2^-128 (include/goalforce.h);
+        // 0 x inf would be the e4m3 NaN code
+        const bool tiny = amax > 0.f && !(448.0f / amax <= FLT_MAX);
+        s_inv[tid] = amax > 0.f ? (tiny ? FLT_MAX : 448.0f / amax) : 0.f;
+        if (t == 0) vscale[h * HD + tid] = tiny ? 0x1p-128f : amax / 448.0f;
     }
     __syncthreads();
 #pragma unroll

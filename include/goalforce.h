@@ -699,6 +699,11 @@ GF_API int gf_vae_upsample2x_padded(const void* x, void* out_interior, int64_t T
  *   q8, q_scale  : int8 codes, one scale per (head, 32 query rows from row 0): scale = amax / 127, code = rne(x * (127 / amax))
  *                  clamped to +-127; an all-zero block has scale 0 and codes 0.  k8, k_scale: the same on k~ per (head, 64 keys)
  *   vt8, v_scale : e4m3fn codes of V^T, one scale per (head, channel) over all keys: scale = amax / 448, code = e4m3(v * (448 / amax))
+ *   tiny blocks  : where the reciprocal 127 / amax (448 / amax) is not finite in fp32 — a non-zero amax below about 3.7e-37 (1.3e-36);
+ *                  bf16 reaches down to 9.2e-41 — the block is quantised with the reciprocal FLT_MAX and gets the scale 2^-128 =
+ *                  fp32(1 / FLT_MAX): every code is finite, a zero element has code 0, code x scale is the element to within the
+ *                  code's own rounding.  Every other block is as stated above, bit for bit.  (Two such scales, s_q s_k = 2^-256,
+ *                  underflow to w = 0: a tiny Q or K block against another attends uniformly — as scores of 1e-74 would.)
  *   s            = float(int32 dot) * fp32(fp32(s_q s_k) * c), c = scale * log2(e)
  *   per 128-key tile in key order: m = running row maximum of s, P = e4m3(exp2(s - m + 8)), l = sum of that P, acc = sum P V_code
  *   (fp32, rescaled by exp2(m_old - m_new) when m moves); O = bf16(acc / l * v_scale)
@@ -722,7 +727,9 @@ GF_API int gf_sage_attn_fwd(const void* q8, const float* q_scale, const void* k8
                             const float* v_scale, void* o, int64_t ldo, int64_t q_len, int64_t kv_len, int64_t heads, float scale,
                             void* stream);
 /* gf_sage_attn — the four quantisation passes and the attention in one call; ws = gf_sage_workspace_bytes bytes, laid out as
- * q8, k8, vt8, q_scale, k_scale, v_scale, mu, scratch, each starting on a 256-byte boundary. */
+ * q8, k8, vt8, q_scale, k_scale, v_scale, mu, scratch, each starting on a 256-byte boundary.  It is its five staged calls in the
+ * order k_mean, quant_q, quant_k, quant_vt, attn_fwd; a refusal of a later stage may follow the earlier stages' writes into ws —
+ * only o is untouched by every refusal. */
 GF_API int gf_sage_attn(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, int vt_in, void* o,
                         int64_t ldo, int64_t q_len, int64_t kv_len, int64_t heads, float scale, void* ws, void* stream);
 

@@ -6,6 +6,8 @@ tests/test_sage_attention_*.py.  Everything is per head on [S, heads*128] tensor
   Q, K~ -> int8 one fp32 scale per (head, block of 32 query rows / 64 keys from row 0): scale = amax / 127,
                 code = rne(x * (127 / amax)) clamped to +-127; an all-zero block: scale 0, codes 0
   V -> e4m3fn   one scale per (head, channel) over all keys: scale = amax / 448, code = e4m3fn_rne(v * (448 / amax))
+  tiny blocks   where 127 / amax (448 / amax) is not finite in fp32 (a non-zero amax below ~3.7e-37 / 1.3e-36): the reciprocal is
+                FLT_MAX and the scale 2^-128 = fp32(1 / FLT_MAX) (include/goalforce.h) — no 0 x inf = NaN
   scores        s = fp32(float(int32 dot) * w), w = fp32(fp32(s_q s_k) * c), c = fp32(fp32(scale) * fp32(log2 e))
   softmax       keys in index order in tiles of T; running maximum m per row, moved when a tile's maximum exceeds it by more than
                 tau (tau = 0: whenever it rises); P = e4m3fn(exp2(s - m + e)) (needs 2^(tau + e) <= 448); l = sum of that P;
@@ -21,6 +23,18 @@ import torch
 HD = 128
 QBLK, KBLK = 32, 64
 E4M3_MAX = 448.0
+FLT_MAX = float(np.finfo(np.float32).max)
+TINY_SCALE = 2.0 ** -128
+
+
+def _inv_scale(amax: torch.Tensor, top: float):
+    """(reciprocal, scale) of a block's amax for the code range `top`: top / amax and amax / top; 0 and 0 for an all-zero block;
+    FLT_MAX and 2^-128 where top / amax overflows fp32 (the header's tiny-block rule)."""
+    top_t = torch.tensor(top, device=amax.device)
+    r = top_t / amax
+    tiny = (amax > 0) & ~(r <= FLT_MAX)
+    inv = torch.where(amax > 0, torch.where(tiny, torch.full_like(r, FLT_MAX), r), torch.zeros_like(amax))
+    return inv, torch.where(tiny, torch.full_like(r, TINY_SCALE), amax / top_t)
 
 
 def softmax_factor(scale: float) -> float:
@@ -40,8 +54,7 @@ def quant_int8(x: torch.Tensor, blk: int):
     xp = torch.zeros((h, nb * blk, HD), dtype=torch.float32, device=x.device)
     xp[:, :s] = x
     amax = xp.reshape(h, nb, blk * HD).abs().amax(dim=2)                            # [H, nb]
-    inv = torch.where(amax > 0, torch.tensor(127.0, device=x.device) / amax, torch.zeros_like(amax))
-    scale = amax / torch.tensor(127.0, device=x.device)
+    inv, scale = _inv_scale(amax, 127.0)
     codes = torch.round(xp * inv.repeat_interleave(blk, dim=1)[:, :, None]).clamp(-127, 127)   # fp32 product, round half to even
     return codes[:, :s].to(torch.int8), scale
 
@@ -59,8 +72,8 @@ def quant_v(v: torch.Tensor, num_heads: int):
     """-> (codes float8_e4m3fn [H, S, 128], scales fp32 [H, 128])."""
     x = _heads(v, num_heads)
     amax = x.abs().amax(dim=1)                                                      # [H, 128]
-    inv = torch.where(amax > 0, torch.tensor(E4M3_MAX, device=x.device) / amax, torch.zeros_like(amax))
-    return (x * inv[:, None, :]).to(torch.float8_e4m3fn), amax / torch.tensor(E4M3_MAX, device=x.device)
+    inv, scale = _inv_scale(amax, E4M3_MAX)
+    return (x * inv[:, None, :]).to(torch.float8_e4m3fn), scale
 
 
 def vt_position(kv_len: int, device=None) -> torch.Tensor:

@@ -9,7 +9,8 @@ row kernels against the exact chains of tests/forward_refs.py, `--only attnfwd` 
 against the bounds of tests/attention_fwd_refs.py, `--only gemmpin` (opt-in) the GEMM family against the exact chain and the two bars
 of tests/gemm_refs.py, `--only vaepin` (opt-in) the VAE's convolution kernels against the plain fp64 convolution of tests/vae_refs.py
 through the same bars, `--only crossfold` (opt-in) the folded cross-attention's two kernels through the raw C ABI against the bars of
-tests/cross_fold_refs.py."""
+tests/cross_fold_refs.py, `--only sagepin` (opt-in) the SageAttention kernels on the exact classes and through the two bars of
+tests/sage_refs.py."""
 import argparse
 import math
 import os
@@ -631,9 +632,75 @@ def case_crossfold(rnd, g):
     return desc, max(err, terr, math.inf if wrote else 0.0), 1.0
 
 
+def case_sagepin(rnd, g):
+    """gf_sage_attn_fwd pinned as tests/test_sage_pinned_gpu.py pins it (helpers: tests/sage_refs.py), through the raw C ABI at a random
+    q_len, kv_len, head count and `ldo` gap, on a random class: one_hot / uniform / staircase (any differing element: inf), gauss (the
+    operands of ops.sage_quant_q / _k / _vt from strided q, k, v, V optionally as the host-built vt32 image; err = the largest of bar
+    (b)'s worst ratio and bar (a)'s share and counts over their caps) or composed (ops.sage_attn on the same inputs: inf unless it
+    equals the staged calls bit for bit, then judged like gauss); a written guard element is inf; bar 1."""
+    if os.path.join(ROOT, "tests") not in sys.path:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import sage_refs as R
+    lib = ops._lib.load()
+    sq = rnd.choice(list(R.Q_LENS) + [rnd.randrange(1, 258)])
+    skv = rnd.choice(list(R.KV_LENS) + [rnd.randrange(1, 514)])
+    heads, gap = rnd.choice([1, 2, 3, 5, 8]), 8 * rnd.choice([0, 1, 2])
+    cls = rnd.choice(["one_hot", "uniform", "staircase", "gauss", "composed"])
+    D, sent = heads * R.HD, 0x5A5A
+    desc = f"sagepin {cls} q={sq} keys={skv} heads={heads} ldo gap {gap}"
+
+    def run(op):
+        dev = [getattr(op, n).cuda() for n in ("q8", "qs", "k8", "ks", "vt8", "vs")]
+        obuf = torch.empty((sq + 1, D + gap), dtype=BF, device="cuda")
+        obuf.view(torch.int16).fill_(sent)
+        ops._lib.check(lib.gf_sage_attn_fwd(*[t.data_ptr() for t in dev], obuf.data_ptr(), D + gap, sq, skv, heads, float(op.scale),
+                                            torch.cuda.current_stream().cuda_stream), "gf_sage_attn_fwd")
+        torch.cuda.synchronize()
+        oi = obuf.view(torch.int16)
+        wrote = bool((oi[sq:] != sent).any()) or bool((oi[:, D:] != sent).any())
+        return obuf[:sq, :D].cpu(), math.inf if wrote else 0.0
+
+    if cls in ("one_hot", "uniform", "staircase"):
+        if cls == "one_hot":
+            op, _, want = R.one_hot(sq, skv, heads, rnd.choice(["first", "last", "spread"]), rnd.randrange(128))
+        elif cls == "uniform":
+            op, want = R.uniform(sq, skv, heads, rnd.choice(["q0", "qs0", "ks0"]), garbage=rnd.random() < 0.5)
+        else:
+            op = R.staircase(sq, -(-skv // 128), heads, skv)
+            want = R.restate(op)
+        got, wrote = run(op)
+        differing = int((got.float() != want.float()).sum())
+        return desc + f" | {differing} elements differ", max(wrote, math.inf if differing else 0.0), 1.0
+
+    def wide(t):                                   # a column slice of a NaN-filled parent, 16-byte aligned
+        off, extra = 8 * rnd.choice([0, 1, 2]), 8 * rnd.choice([0, 1, 3])
+        big = torch.full((t.shape[0] + 2, off + t.shape[1] + extra), float("nan"), dtype=BF, device="cuda")
+        big[:t.shape[0], off:off + t.shape[1]] = t.cuda()
+        return big[:t.shape[0], off:off + t.shape[1]]
+
+    qc, kc, vc = R.gauss_qkv(sq, skv, heads, rnd.choice([1.0, 3.0]), rnd.randrange(1000), rnd.random() < 0.5)
+    q, k, v = wide(qc), wide(kc), wide(vc)
+    vt = R.vt32_of(vc).cuda().reshape(-1) if rnd.random() < 0.5 else None
+    q8, qs = ops.sage_quant_q(q, heads)
+    k8, ks, _ = ops.sage_quant_k(k, heads)
+    vt8, vs = ops.sage_quant_vt(v, heads) if vt is None else ops.sage_quant_vt(None, heads, vt=vt, kv_len=skv)
+    op = R.Ops(q8.cpu(), qs.cpu(), k8.cpu(), ks.cpu(), vt8.cpu(), vs.cpu(), sq, skv, heads, R.HD ** -0.5)
+    got, wrote = run(op)
+    desc += f" vt_in={int(vt is not None)}"
+    if cls == "composed":
+        whole = ops.sage_attn(q, k, v if vt is None else None, heads, vt=vt).cpu()
+        if not torch.equal(whole.view(torch.int16), got.view(torch.int16)):
+            return desc + " | gf_sage_attn is not its staged calls", math.inf, 1.0
+    j = R.judge(got, R.recipe(op))
+    a_err = (math.inf if j["differing"] else 0.0) if j["rate"] * j["numel"] < 1 else j["share"] / j["rate"]
+    err = max(wrote, a_err, j["pair_worst"] / j["pair_cap"], math.inf if j["col_over"] else 0.0, j["worst"], j["excused"] / R.EXCUSED_CAP)
+    return desc + " | " + R.describe(j), err, 1.0
+
+
 CASES = {"gemmpin": case_gemmpin, "vaepin": case_vaepin, "gemm": case_gemm, "attn": case_attn, "rows": case_rows, "cfg": case_cfg, "attnbwd": case_attnbwd, "fp8": case_fp8,
-         "batched": case_batched, "misc": case_misc, "bwdrows": case_bwdrows, "fwdrows": case_fwdrows, "attnfwd": case_attnfwd, "crossfold": case_crossfold}
-OPT_IN = ("fwdrows", "attnfwd", "gemmpin", "vaepin", "crossfold")       # run with --only alone (bwdrows is in the default sweep): the default sweep, and the suite's run of it, stays what it was
+         "batched": case_batched, "misc": case_misc, "bwdrows": case_bwdrows, "fwdrows": case_fwdrows, "attnfwd": case_attnfwd, "crossfold": case_crossfold,
+         "sagepin": case_sagepin}
+OPT_IN = ("fwdrows", "attnfwd", "gemmpin", "vaepin", "crossfold", "sagepin")       # run with --only alone (bwdrows is in the default sweep): the default sweep, and the suite's run of it, stays what it was
 
 
 def main():
