@@ -2,8 +2,20 @@
 `pipe.model_fn`, src/goal_force/wan_video_new.py:161, 1349-1591), rebuilt on the HIP kernels.
 
 Same keyword interface as the reference; branches the Goal-Force inference scripts never take
-(S2V, VACE, camera/motion control, sliding window, reference latents, cfg-merged batches)
+(S2V, VACE, camera/motion control, reference latents, cfg-merged batches)
 raise NotImplementedError instead of silently doing something else.
+
+`sliding_window_size` / `sliding_window_stride` (GF:1381-1405): the forward is evaluated on overlapping windows of latent frames
+and the predictions are cross-faded by temporal_tiler.TemporalTiler_BCTHW — the reference's schedule, mask and bf16 roundings, blended
+on the device (gf_window.hip).  `latents` and `y` are cut along T as in the reference.  ONE DEPARTURE: the reference's window
+keywords (GF:1382-1397) carry neither `controlnet` nor `control_signal_video_latents`, so its windowed forward silently samples
+WITHOUT the force control (tests/golden/make_sliding_window_golden.py asserts that, bit for bit); here the ControlNet follows its
+window: `control_signal_video_latents` is cut along T with the latents.  `context_cache`, `elide_zero_controlnet` and `sparse_dense`
+pass through to every window (the text memo is the same for all of them, RoPE tables are memoised per grid); `cfg_shared` gets one
+sub-dict per window start, so the uncond window t takes the block-0 halves of the cond window t.  Refused by message with a window:
+`tea_cache` (the reference hands ONE TeaCache to every window, whose step counter then advances once per window, not per step) and
+sequence parallelism (never run).  Only one of the two values, a stride above the size or a non-positive / non-integer value is
+refused by name; the reference ignores the first and crashes or divides by a zero weight on the others.
 
 Differences that do not change results:
   * RoPE tables live on the device and are built once per grid (the reference rebuilds them on the CPU
@@ -37,6 +49,7 @@ import torch
 from . import ops
 from ._lib import GoalForceError
 from .dit import WanModel, pad_run
+from .temporal_tiler import TemporalTiler_BCTHW, check_window
 
 
 class ContextCache:
@@ -97,10 +110,33 @@ def model_fn_wan_video(
 ):
     for name, val in (("motion_controller", motion_controller), ("vace", vace), ("reference_latents", reference_latents),
                       ("vace_context", vace_context), ("audio_embeds", audio_embeds),
-                      ("motion_bucket_id", motion_bucket_id), ("sliding_window_size", sliding_window_size),
+                      ("motion_bucket_id", motion_bucket_id),
                       ("control_camera_latents_input", control_camera_latents_input),
                       ("clip_feature", clip_feature if dit.require_clip_embedding else None)):
         _unsupported(name, val)
+    window = check_window(sliding_window_size, sliding_window_stride)
+    if window is not None:                  # GF:1381-1405 — see the module docstring
+        if tea_cache is not None:
+            raise GoalForceError("model_fn_wan_video: tea_cache with a sliding window is not built (the reference hands one TeaCache to "
+                                 "every window, so its step counter advances once per window, GF:1394)")
+        if use_unified_sequence_parallel or sequence_parallel is not None:
+            raise GoalForceError("model_fn_wan_video: sequence parallelism with a sliding window is not built (never run on more than "
+                                 "one GPU)")
+        if cfg_merge:
+            raise NotImplementedError("cfg_merge / batch > 1: run the cond and uncond forwards separately (GF:710-716)")
+        if not latents.is_cuda:
+            raise GoalForceError("model_fn_wan_video: tensors must be on the GPU (no CPU fallback exists)")
+        model_kwargs = dict(dit=dit, latents=latents, timestep=timestep, context=context, clip_feature=clip_feature, y=y,
+                            fuse_vae_embedding_in_latents=fuse_vae_embedding_in_latents, controlnet=controlnet,
+                            context_cache=context_cache, elide_zero_controlnet=elide_zero_controlnet, sparse_dense=sparse_dense,
+                            **kwargs)
+
+        def per_window(t, t_):               # window t of the second CFG branch drains what window t of the first one stored
+            return {} if cfg_shared is None else {"cfg_shared": cfg_shared.setdefault(("window", t), {})}
+        return TemporalTiler_BCTHW().run(
+            model_fn_wan_video, *window, latents.device, latents.dtype, model_kwargs=model_kwargs,
+            tensor_names=["latents", "y"] + (["control_signal_video_latents"] if controlnet is not None else []),
+            batch_size=1, window_kwargs=per_window)
     sp = sequence_parallel
     if use_unified_sequence_parallel and sp is None:
         from .sequence_parallel import SequenceParallel

@@ -1456,6 +1456,52 @@ def vae_tile_finalize(values, weight, clamp=True):
     return values
 
 
+def _window_value(op, value, weight):
+    """The accumulators of a sliding-window blend: value [C, T, *spatial] bf16 (a leading batch dim of 1 is taken off) whose
+    spatial dims are contiguous — C and T may be strided, a slice of a larger tensor — and weight [T] bf16 contiguous
+    -> (value as [C, T, ...], C, T, HW, stride of C, stride of T)."""
+    _req(value, f"{op}.value")
+    if value.dim() == 5 and value.shape[0] == 1:
+        value = value[0]
+    if value.dim() < 3 or value.numel() == 0:
+        raise GoalForceError(f"{op}.value: expected a non-empty [C, T, ...] (or [1, C, T, H, W]), got {tuple(value.shape)}")
+    C, T = value.shape[:2]
+    HW = math.prod(value.shape[2:])
+    inner = 1
+    for d in range(value.dim() - 1, 1, -1):
+        if value.shape[d] != 1 and value.stride(d) != inner:
+            raise GoalForceError(f"{op}.value: the dims after T must be contiguous")
+        inner *= value.shape[d]
+    sc, st = value.stride(0), value.stride(1)
+    if st < HW or sc < (T - 1) * st + HW:
+        raise GoalForceError(f"{op}.value: the [T, ...] planes of the channels overlap (strides {tuple(value.stride())})")
+    _vec(weight, f"{op}.weight", T, required=True)
+    return value, C, T, HW, sc, st
+
+
+def window_blend(value, weight, win, t0, bounds, border):
+    """One temporal window into the accumulators of TemporalTiler_BCTHW.run (gf_window_blend): value [C, T, ...] += win * mask,
+    weight [T] += mask, every op rounded to bf16.  win [C, len, ...] (or [1, C, len, H, W]) is the window's prediction for frames
+    t0 .. t0+len-1; bounds = (left, right): the window touches that end of the clip (no ramp there); border = size - stride."""
+    value, C, T, HW, sc, st = _window_value("window_blend", value, weight)
+    _req(win, "window_blend.win")
+    if win.dim() == 5 and win.shape[0] == 1:
+        win = win[0]
+    if win.dim() != value.dim() or win.shape[0] != C or win.shape[2:] != value.shape[2:] or not win.is_contiguous():
+        raise GoalForceError(f"window_blend.win: expected contiguous [{C}, len, {', '.join(map(str, value.shape[2:]))}], "
+                             f"got {tuple(win.shape)}")
+    _lib.check(_lib.load().gf_window_blend(_ptr(value), _ptr(weight), _ptr(win), C, T, HW, sc, st, int(t0), win.shape[1],
+                                           int(bool(bounds[0])), int(bool(bounds[1])), int(border), _stream(value)),
+               "gf_window_blend")
+
+
+def window_finalize(value, weight):
+    """In place: value[c, t] /= weight[t], one bf16 rounding, no clamp (gf_window_finalize); returns value."""
+    v, C, T, HW, sc, st = _window_value("window_finalize", value, weight)
+    _lib.check(_lib.load().gf_window_finalize(_ptr(v), _ptr(weight), C, T, HW, sc, st, _stream(v)), "gf_window_finalize")
+    return value
+
+
 # ---------------------------------------------------------------------------------- fp8 Linear (VRAM:115-151)
 
 

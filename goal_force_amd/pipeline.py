@@ -27,6 +27,7 @@ from .dit import A14B_CONFIG, WanModel
 from .model_fn import ContextCache, model_fn_wan_video
 from .scheduler import FlowMatchScheduler
 from .teacache import TeaCache, coefficients_for  # noqa: F401  (TeaCache: re-exported, it lives beside the pipeline in the reference)
+from .temporal_tiler import TemporalTiler_BCTHW, check_window  # noqa: F401  (TemporalTiler_BCTHW: re-exported like TeaCache)
 
 
 class WanVideoPipeline(torch.nn.Module):
@@ -272,7 +273,8 @@ class WanVideoPipeline(torch.nn.Module):
     def denoise(self, latents, context_posi, context_nega, y, control_signal_video_latents, num_inference_steps=50,
                 cfg_scale=5.0, switch_DiT_boundary=0.875, sigma_shift=5.0, denoising_strength=1.0, controlnet=True,
                 progress_bar_cmd=None, record_step_times=False, step_ids=None, cfg_parallel=None,
-                sequence_parallel=None, tea_cache_l1_thresh=None, tea_cache_model_id=""):
+                sequence_parallel=None, tea_cache_l1_thresh=None, tea_cache_model_id="", sliding_window_size=None,
+                sliding_window_stride=None):
         """GF:663 + GF:697-723.  Returns the final latents [1,16,f,H/8,W/8] (a new tensor).
         `step_ids` (optional) restricts the loop to a sub-range of the schedule (benchmarks).
         `cfg_parallel` (distributed.CfgPairParallel): this rank computes only its branch of the CFG pair and
@@ -281,7 +283,10 @@ class WanVideoPipeline(torch.nn.Module):
         head-parallel attention; the noise prediction comes back whole on every rank of the group.
         `tea_cache_l1_thresh` / `tea_cache_model_id` (GF:1114-1125): one teacache.TeaCache per CFG branch for this call, shared by
         both experts; None = off — no object, and the loop is today's.  The decision is a function of the timestep and the expert
-        only, so both ranks of a `cfg_parallel` pair decide alike and each exchanges its prediction either way."""
+        only, so both ranks of a `cfg_parallel` pair decide alike and each exchanges its prediction either way.
+        `sliding_window_size` / `sliding_window_stride` (GF:1381-1405, in latent frames): every forward is evaluated on overlapping
+        temporal windows and cross-faded (model_fn_wan_video; temporal_tiler.py); the prediction keeps the dense shape."""
+        check_window(sliding_window_size, sliding_window_stride)      # a malformed request is refused before any work is done
         tea_kw = ({}, {})                    # extra keywords of the [cond, uncond] forward
         if tea_cache_l1_thresh is not None:
             tea_kw = tuple({"tea_cache": TeaCache(num_inference_steps, rel_l1_thresh=tea_cache_l1_thresh, model_id=tea_cache_model_id)}
@@ -312,6 +317,8 @@ class WanVideoPipeline(torch.nn.Module):
                           elide_zero_controlnet=self.elide_zero_controlnet)
             if progress_id < self.sparse_dense_steps:
                 shared["sparse_dense"] = True         # (only passed when set: a caller's own model_fn need not know the keyword)
+            if sliding_window_size is not None:
+                shared.update(sliding_window_size=sliding_window_size, sliding_window_stride=sliding_window_stride)
             if sequence_parallel is not None:
                 shared["sequence_parallel"] = sequence_parallel
             elif getattr(self, "use_unified_sequence_parallel", False):
@@ -378,13 +385,14 @@ class WanVideoPipeline(torch.nn.Module):
                           ("motion_video", motion_video), ("control_video", control_video),
                           ("reference_image", reference_image), ("camera_control_direction", camera_control_direction),
                           ("vace_video", vace_video), ("vace_reference_image", vace_reference_image),
-                          ("motion_bucket_id", motion_bucket_id), ("sliding_window_size", sliding_window_size)):
+                          ("motion_bucket_id", motion_bucket_id)):
             if val is not None:
                 raise NotImplementedError(f"`{name}` belongs to a pipeline branch Goal Force never takes (SURVEY §2 #2)")
         if cfg_merge:
             raise NotImplementedError("cfg_merge=True: the reference default (two sequential forwards) is what is built")
         if tea_cache_l1_thresh is not None:
             coefficients_for(tea_cache_model_id)       # an unknown id is a ValueError before any work is done (GF:1259-1261)
+        check_window(sliding_window_size, sliding_window_stride)     # (as is a malformed window, before the encoders run)
         height, width, num_frames = self.check_resize_height_width(height, width, num_frames)
         length = (num_frames - 1) // 4 + 1
         noise = self.generate_noise((1, 16, length, height // 8, width // 8), seed=seed, rand_device=rand_device)
@@ -419,7 +427,8 @@ class WanVideoPipeline(torch.nn.Module):
                                denoising_strength=denoising_strength, controlnet=controlnet,
                                progress_bar_cmd=progress_bar_cmd, cfg_parallel=cfg_parallel,
                                sequence_parallel=sequence_parallel, tea_cache_l1_thresh=tea_cache_l1_thresh,
-                               tea_cache_model_id=tea_cache_model_id)
+                               tea_cache_model_id=tea_cache_model_id, sliding_window_size=sliding_window_size,
+                               sliding_window_stride=sliding_window_stride)
         if output_type == "latent":
             return latents
         if self.vae is None:

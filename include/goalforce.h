@@ -538,6 +538,30 @@ GF_API int gf_vae_tile_blend(void* values, void* weight, const void* tile, int64
 /* clamp1 != 0: clamp to [-1,1] (decode); 0: no clamp (tiled_encode, VAE:1155-1203). */
 GF_API int gf_vae_tile_finalize(void* values, const void* weight, int64_t planes, int64_t hw, int clamp1, void* stream);
 
+/* gf_window_blend / gf_window_finalize — TemporalTiler_BCTHW.run's weighted accumulation of one temporal window (GF:1336-1343,
+ * build_1d_mask GF:1300-1310) with bf16 accumulators: the sibling in time of gf_vae_tile_blend / gf_vae_tile_finalize.
+ *   value  [C, T, HW] bf16, HW contiguous, value_stride_c / value_stride_t in elements (a slice of a larger tensor is fine as long
+ *          as its planes do not overlap); weight [T] bf16.  Both are accumulators, zeroed by the caller before the first window.
+ *   win    [C, len, HW] bf16 contiguous: the window's prediction as gf_unpatchify leaves it; it covers frames t0 .. t0+len-1.
+ * The mask of window frame i, built in this order (the right ramp is written last and wins where both apply, len < 2*border):
+ *   m = 1
+ *   if (!left_bound  && i < border)        m = bf16(fp32(i + 0.5) / fp32(border))
+ *   if (!right_bound && i >= len - border) m = bf16(fp32(len - 1 - i + 0.5) / fp32(border))
+ * (the fp32 division correctly rounded; border = 0: all ones), and the update, the reference's two bf16 roundings of
+ * `value += out * mask`:
+ *   value[c, t0+i, p] = bf16(fp32(value[c, t0+i, p]) + fp32(bf16(fp32(win[c, i, p]) * fp32(m))))
+ *   weight[t0+i]      = bf16(fp32(weight[t0+i]) + fp32(m))
+ * Windows of one accumulator are blended on one stream in ascending t0: bf16 accumulation depends on the order.
+ * Refused (outputs untouched): null pointers, C / T / HW / len <= 0, strides that let planes overlap, t0 < 0, t0 + len > T,
+ * border < 0, and border >= len when a ramp is requested (!left_bound || !right_bound, border > 0). */
+GF_API int gf_window_blend(void* value, void* weight, const void* win, int64_t C, int64_t T, int64_t HW, int64_t value_stride_c,
+                           int64_t value_stride_t, int64_t t0, int64_t len, int left_bound, int right_bound, int64_t border,
+                           void* stream);
+/* value[c, t, p] = bf16(fp32(value[c, t, p]) / fp32(weight[t])), no clamp (GF:1343); a frame no window covered divides by zero
+ * as the reference does. */
+GF_API int gf_window_finalize(void* value, const void* weight, int64_t C, int64_t T, int64_t HW, int64_t value_stride_c,
+                              int64_t value_stride_t, void* stream);
+
 /* gf_modulate — the reference's module-level `modulate(x, shift, scale)` (DIT:64-65) in its eager bf16 rounding sequence:
  * out = bf16(bf16(x * bf16(1 + scale)) + shift); scale / shift [dim] bf16; x, out [rows, dim] bf16.  (On the hot path the
  * modulation is fused into gf_layernorm_modulate; this entry point backs the B3 drop-in name.) */
