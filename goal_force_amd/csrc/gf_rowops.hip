@@ -10,6 +10,7 @@
 //   rope_apply on adjacent pairs ................ diffsynth/models/wan_video_dit.py:92-97
 #include "gf_common.h"
 #include "gf_mxfp4_quant.h"
+#include <type_traits>
 
 namespace {
 
@@ -138,13 +139,44 @@ __global__ __launch_bounds__(ROW_THREADS) void rmsnorm_rope_kernel(
 // the 128-thread kernels above stay for every other width.
 constexpr int WROWS = 4;
 
-// MX4: the row goes out as MXFP4 (gf_mxfp4_quant.h) — `out` is then the packed codes with out_stride in BYTES, `scales` / scale_stride
-// the E8M0 bytes; a lane's 8 columns are a quarter of an MX block and the block's scale is local to the chunk, so nothing is kept.
-template <int NCH, bool MX4 = false>
+// What a LayerNorm entry point writes: bf16 rows; e4m3 rows + one fp32 scale per row (the fp8_linear input); MXFP4 codes + E8M0 scales.
+enum { LN_BF16, LN_FP8, LN_MX4 };
+
+// The fp8 activation quantisation of AutoWrappedLinear.fp8_linear (VRAM:115-140), from a row's maximum |x|:
+//   scale_a = clamp(rowmax|x| / 448, min=1)  (fp32);   x8 = e4m3(float(x) / (scale_a + 1e-8))
+// x_max is a bf16 tensor in the reference, so x_max / 448 is rounded to bf16 before clamp(min=1).float().  OCP e4m3fn on gfx950 (not
+// MI300's fnuz).  `unit`: 1 + 1e-8 IS 1 in fp32, so x / den = x exactly and a kernel may leave the divisions out.
+struct Fp8RowScale {
+    float den;
+    bool unit;
+    __device__ __forceinline__ static float scale_a(float mx) { return fmaxf(rbf(mx / 448.0f), 1.0f); }
+    __device__ __forceinline__ explicit Fp8RowScale(float sc) : den(sc + 1e-8f), unit(den == 1.0f) {}
+    // four / eight values, already divided by den -> their e4m3 bytes in column order
+    __device__ __forceinline__ static unsigned pack4(float f0, float f1, float f2, float f3) {
+        unsigned w = 0;
+        w = __builtin_amdgcn_cvt_pk_fp8_f32(f0, f1, w, false);
+        return __builtin_amdgcn_cvt_pk_fp8_f32(f2, f3, w, true);
+    }
+    __device__ __forceinline__ static u32x2 pack(const float (&f)[8]) { return u32x2{pack4(f[0], f[1], f[2], f[3]), pack4(f[4], f[5], f[6], f[7])}; }
+};
+
+// The operand set is decided per element (any subset of weight / bias / scale1p / shift); OUT chooses the store:
+//   LN_BF16: the bf16 row.
+//   LN_FP8:  the consumer is an fp8 Linear (BASELINE config 5): the bf16 row the reference would hand to fp8_linear never goes to HBM —
+//            the wave that normalised it takes its row maximum (wave shuffles), forms scale_a (`scale`, fp32 per row) and writes the
+//            e4m3 bytes.  Same arithmetic, in the same order, as the LN_BF16 kernel followed by quant_fp8_rowscale_kernel
+//            (bit-identical: tests/test_fp8.py), one 335 MB write and one 335 MB read less per use.
+//   LN_MX4:  the row goes out as MXFP4 (gf_mxfp4_quant.h) — `out` is then the packed codes with out_stride in BYTES, mx_scales /
+//            mx_stride the E8M0 bytes; a lane's 8 columns are a quarter of an MX block and the block's scale is local to the chunk, so
+//            nothing is kept.
+// `Scale` is <float> for LN_FP8 and empty otherwise: the row-scale pointer is an argument of that kind alone, third as it always was.
+// Behind eps it gave the fp8 kind other kernel-argument offsets and register numbers (profiles/r22: the instruction streams are pinned).
+template <int NCH, int OUT, class... Scale>
 __global__ __launch_bounds__(64 * WROWS) void layernorm_modulate_wave_kernel(
-    const u16* __restrict__ x, u16* __restrict__ out, const u16* __restrict__ weight, const u16* __restrict__ bias,
-    const u16* __restrict__ scale1p, const u16* __restrict__ shift, long rows, long x_stride, long out_stride, float eps,
-    unsigned char* __restrict__ scales = nullptr, long scale_stride = 0) {
+    const u16* __restrict__ x, void* __restrict__ out, Scale* __restrict__... scale, const u16* __restrict__ weight,
+    const u16* __restrict__ bias, const u16* __restrict__ scale1p, const u16* __restrict__ shift, long rows, long x_stride, long out_stride,
+    float eps, unsigned char* __restrict__ mx_scales = nullptr, long mx_stride = 0) {
+    static_assert(sizeof...(Scale) == (OUT == LN_FP8), "the row scales belong to the fp8 kind");
     constexpr int DIM = NCH * 512;
     const long row = (long)blockIdx.x * WROWS + (threadIdx.x >> 6);
     if (row >= rows) return;
@@ -168,11 +200,13 @@ __global__ __launch_bounds__(64 * WROWS) void layernorm_modulate_wave_kernel(
             q = __builtin_fmaf(d, d, q);   // written out: left to fp-contract, `q += d * d` may fuse the first two squares either way round
         }
     const float rstd = 1.0f / sqrtf(__builtin_fmaf(wave_sum(q), 1.0f / DIM, eps));
-    u16* orow = MX4 ? nullptr : out + row * out_stride + lane * 8;
+    u16* orow = OUT == LN_BF16 ? (u16*)out + row * out_stride + lane * 8 : nullptr;
+    float mx = 0.f;
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
         const int c0 = i * 512 + lane * 8;
-        u16x8 w8, b8, sc8, sh8, o;
+        u16x8 w8, b8, sc8, sh8, o_;
+        u16x8& o = OUT == LN_FP8 ? v[i] : o_;    // fp8: the bf16 row fp8_linear receives replaces the input in its registers
         if (weight) w8 = *reinterpret_cast<const u16x8*>(weight + c0);
         if (bias) b8 = *reinterpret_cast<const u16x8*>(bias + c0);
         if (scale1p) sc8 = *reinterpret_cast<const u16x8*>(scale1p + c0);
@@ -186,13 +220,29 @@ __global__ __launch_bounds__(64 * WROWS) void layernorm_modulate_wave_kernel(
             if (scale1p) y = rbf(y * bf2f(sc8[j]));       // x * (1 + scale)
             if (shift) y = rbf(y + bf2f(sh8[j]));         // + shift
             o[j] = f2bf(y);
+            if constexpr (OUT == LN_FP8) mx = fmaxf(mx, fabsf(y));
         }
-        if constexpr (MX4) {   // the whole wave is here (row is wave-uniform): all four lanes of every block take the step's shuffles
+        if constexpr (OUT == LN_MX4) {      // the whole wave is here (row is wave-uniform): all four lanes of every block take the step's shuffles
             int code;
             const unsigned packed = mxfp4_block_step(o, code);
             *reinterpret_cast<unsigned*>((unsigned char*)out + row * out_stride + (c0 >> 1)) = packed;
-            if ((lane & 3) == 0) scales[row * scale_stride + (c0 >> 5)] = (unsigned char)code;
-        } else *reinterpret_cast<u16x8*>(orow + i * 512) = o;
+            if ((lane & 3) == 0) mx_scales[row * mx_stride + (c0 >> 5)] = (unsigned char)code;
+        } else if constexpr (OUT == LN_BF16) *reinterpret_cast<u16x8*>(orow + i * 512) = o;
+    }
+    if constexpr (OUT == LN_FP8) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+        const float sc = Fp8RowScale::scale_a(mx);
+        if (lane == 0) ((scale[row] = sc), ...);     // (the one pointer of the pack)
+        const Fp8RowScale fq(sc);
+        unsigned char* orow8 = (unsigned char*)out + row * out_stride + lane * 8;
+#pragma unroll
+        for (int i = 0; i < NCH; ++i) {
+            float f[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) f[j] = fq.unit ? bf2f(v[i][j]) : bf2f(v[i][j]) / fq.den;   // (unit is wave-uniform)
+            *reinterpret_cast<u32x2*>(orow8 + i * 512) = Fp8RowScale::pack(f);
+        }
     }
 }
 
@@ -205,7 +255,7 @@ __global__ __launch_bounds__(64 * WROWS) void layernorm_modulate_wave_kernel(
 //   MODE 0: LayerNorm                      (norm without affine, no modulation)
 //   MODE 1: LayerNorm * a + b              (a = weight, b = bias: norm3)
 //   MODE 2: modulate(LayerNorm, b, a)      (a = 1 + scale, b = shift: norm1 / norm2 / head, the reference's three bf16 roundings)
-//   FP8: the result is quantised in registers for an fp8_linear consumer (layernorm_modulate_fp8_wave_kernel's contract).
+//   FP8: the result is quantised in registers for an fp8_linear consumer (layernorm_modulate_wave_kernel<NCH, LN_FP8>'s contract).
 //   MX4: the result is quantised to MXFP4 in registers for an fp4 Linear (gf_mxfp4_quant.h): outp = the packed codes, out_stride in
 //        bytes, mx_scales / mx_stride the E8M0 bytes.  The scale is local to a 32-column block = four lanes of one chunk, so each chunk
 //        is quantised and stored inside the chunk loop.
@@ -309,10 +359,9 @@ __global__ __launch_bounds__(64 * WROWS) void layernorm_wave2_kernel(const u16* 
         float mx = bf2f(mxb[0] > mxb[1] ? mxb[0] : mxb[1]);
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-        const float sc = fmaxf(rbf(mx / 448.0f), 1.0f);      // x_max is bf16 in the reference: x_max / 448 rounds to bf16 before the clamp
+        const float sc = Fp8RowScale::scale_a(mx);
         if (lane == 0) scale_out[row] = sc;
-        const float den = sc + 1e-8f;
-        const bool unit = den == 1.0f;                       // wave-uniform; 1 + 1e-8 IS 1 in fp32, so x / den = x exactly
+        const Fp8RowScale fq(sc);
         unsigned char* orow = (unsigned char*)outp + row * out_stride + lane * 8;
 #pragma unroll
         for (int i = 0; i < NCH; ++i) {
@@ -320,14 +369,11 @@ __global__ __launch_bounds__(64 * WROWS) void layernorm_wave2_kernel(const u16* 
 #pragma unroll
             for (int h2 = 0; h2 < 2; ++h2) {
                 gf_f32x2 f0 = unpack2bf(v[i][2 * h2]), f1 = unpack2bf(v[i][2 * h2 + 1]);
-                if (!unit) {
-                    f0 = gf_f32x2{f0[0] / den, f0[1] / den};
-                    f1 = gf_f32x2{f1[0] / den, f1[1] / den};
+                if (!fq.unit) {                  // (wave-uniform)
+                    f0 = gf_f32x2{f0[0] / fq.den, f0[1] / fq.den};
+                    f1 = gf_f32x2{f1[0] / fq.den, f1[1] / fq.den};
                 }
-                unsigned t = 0;
-                t = __builtin_amdgcn_cvt_pk_fp8_f32(f0[0], f0[1], t, false);
-                t = __builtin_amdgcn_cvt_pk_fp8_f32(f1[0], f1[1], t, true);
-                w[h2] = t;
+                w[h2] = Fp8RowScale::pack4(f0[0], f0[1], f1[0], f1[1]);
             }
             *reinterpret_cast<u32x2*>(orow + i * 512) = u32x2{w[0], w[1]};
         }
@@ -399,9 +445,7 @@ __global__ __launch_bounds__(64 * WROWS) void rmsnorm_rope_wave_kernel(u16* __re
     }
 }
 
-// fp8 activation quantisation of AutoWrappedLinear.fp8_linear (VRAM:115-140):
-//   scale_a = clamp(rowmax|x| / 448, min=1)  (fp32);   x8 = e4m3(float(x) / (scale_a + 1e-8))
-// OCP e4m3fn on gfx950 (not MI300's fnuz).  One workgroup per row, row kept in registers.
+// The fp8_linear activation quantisation (Fp8RowScale) on its own.  One workgroup per row, row kept in registers.
 __global__ __launch_bounds__(ROW_THREADS) void quant_fp8_rowscale_kernel(const u16* __restrict__ x,
                                                                          unsigned char* __restrict__ out,
                                                                          float* __restrict__ scale, int dim,
@@ -428,10 +472,9 @@ __global__ __launch_bounds__(ROW_THREADS) void quant_fp8_rowscale_kernel(const u
     if ((tid & 63) == 0) red[tid >> 6] = mx;
     __syncthreads();
     mx = fmaxf(red[0], red[1]);
-    // x_max is a bf16 tensor in the reference, so x_max / 448 is rounded to bf16 before clamp(min=1).float()
-    const float sc = fmaxf(rbf(mx / 448.0f), 1.0f);
+    const float sc = Fp8RowScale::scale_a(mx);
     if (tid == 0) scale[row] = sc;
-    const float den = sc + 1e-8f;
+    const Fp8RowScale fq(sc);
     unsigned char* orow = out + row * out_stride;
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
@@ -439,88 +482,9 @@ __global__ __launch_bounds__(ROW_THREADS) void quant_fp8_rowscale_kernel(const u
         if (c < nchunks) {
             float f[8];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) f[j] = bf2f(v[i][j]) / den;
-            unsigned w0 = 0, w1 = 0;
-            w0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], w0, false);
-            w0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], w0, true);
-            w1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], w1, false);
-            w1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], w1, true);
-            *reinterpret_cast<u32x2*>(orow + (c << 3)) = u32x2{w0, w1};
+            for (int j = 0; j < 8; ++j) f[j] = bf2f(v[i][j]) / fq.den;   // (no `unit` shortcut here)
+            *reinterpret_cast<u32x2*>(orow + (c << 3)) = Fp8RowScale::pack(f);
         }
-    }
-}
-
-// LayerNorm(+affine)(+modulate) whose consumer is an fp8 Linear (BASELINE config 5): the bf16 row the reference would hand to
-// fp8_linear never goes to HBM — the wave that normalised it takes its row maximum (wave shuffles), forms scale_a and writes the
-// e4m3 bytes + the scale.  Same arithmetic, in the same order, as layernorm_modulate_wave_kernel followed by
-// quant_fp8_rowscale_kernel (bit-identical: tests/test_fp8.py), one 335 MB write and one 335 MB read less per use.
-template <int NCH>
-__global__ __launch_bounds__(64 * WROWS) void layernorm_modulate_fp8_wave_kernel(
-    const u16* __restrict__ x, unsigned char* __restrict__ out8, float* __restrict__ scale, const u16* __restrict__ weight,
-    const u16* __restrict__ bias, const u16* __restrict__ scale1p, const u16* __restrict__ shift, long rows, long x_stride,
-    long out_stride, float eps) {
-    constexpr int DIM = NCH * 512;
-    const long row = (long)blockIdx.x * WROWS + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int lane = threadIdx.x & 63;
-    const u16* xr = x + row * x_stride + lane * 8;
-    u16x8 v[NCH];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-        v[i] = *reinterpret_cast<const u16x8*>(xr + i * 512);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) s += bf2f(v[i][j]);
-    }
-    const float mean = wave_sum(s) / (float)DIM;   // correctly rounded (not sum * rounded 1 / DIM): a constant row gives exactly 0
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < NCH; ++i)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float d = bf2f(v[i][j]) - mean;
-            q = __builtin_fmaf(d, d, q);   // written out: left to fp-contract, `q += d * d` may fuse the first two squares either way round
-        }
-    const float rstd = 1.0f / sqrtf(__builtin_fmaf(wave_sum(q), 1.0f / DIM, eps));
-    float mx = 0.f;
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-        const int c0 = i * 512 + lane * 8;
-        u16x8 w8, b8, sc8, sh8;
-        if (weight) w8 = *reinterpret_cast<const u16x8*>(weight + c0);
-        if (bias) b8 = *reinterpret_cast<const u16x8*>(bias + c0);
-        if (scale1p) sc8 = *reinterpret_cast<const u16x8*>(scale1p + c0);
-        if (shift) sh8 = *reinterpret_cast<const u16x8*>(shift + c0);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            float y = (bf2f(v[i][j]) - mean) * rstd;
-            if (weight) y = y * bf2f(w8[j]);
-            if (bias) y = y + bf2f(b8[j]);
-            y = rbf(y);                                   // .type_as(x)
-            if (scale1p) y = rbf(y * bf2f(sc8[j]));       // x * (1 + scale)
-            if (shift) y = rbf(y + bf2f(sh8[j]));         // + shift
-            v[i][j] = f2bf(y);                            // the bf16 row fp8_linear receives (kept in registers)
-            mx = fmaxf(mx, fabsf(y));
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-    const float sc = fmaxf(rbf(mx / 448.0f), 1.0f);      // x_max is bf16 in the reference: x_max / 448 rounds to bf16 before the clamp
-    if (lane == 0) scale[row] = sc;
-    const float den = sc + 1e-8f;
-    const bool unit = den == 1.0f;                       // wave-uniform; 1 + 1e-8 IS 1 in fp32, so x / den = x exactly
-    unsigned char* orow = out8 + row * out_stride + lane * 8;
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-        float f[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) f[j] = unit ? bf2f(v[i][j]) : bf2f(v[i][j]) / den;
-        unsigned w0 = 0, w1 = 0;
-        w0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], w0, false);
-        w0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], w0, true);
-        w1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], w1, false);
-        w1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], w1, true);
-        *reinterpret_cast<u32x2*>(orow + i * 512) = u32x2{w0, w1};
     }
 }
 
@@ -575,137 +539,97 @@ extern "C" GF_API int gf_cast_fp8(const void* x, void* out8, int64_t n, void* st
     return GF_OK;
 }
 
+namespace {
+
+// f(std::integral_constant<int, V>{}) for the listed V that equals v -> true; false, and no call, when none does
+template <int... Vs, class F>
+bool ln_pick(int64_t v, F&& f) {
+    return ((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...);
+}
+
+// The three LayerNorm entry points: `fn` names the entry in its refusals, OUT is what it writes (`out`: bf16 rows / e4m3 rows / packed
+// MXFP4 codes with out_stride in bytes; `aux`: nothing / the fp32 row scales / the E8M0 bytes with aux_stride).  Each entry's own
+// rules stand where they stood among the shared ones.  The kernel: at the wave-per-row widths the specialised one for the three
+// operand sets of the DiT (plain, weight + bias, scale + shift) and the generic wave kernel for any other subset; at every other
+// width — which only the bf16 entry accepts — the workgroup-per-row kernel.
+template <int OUT>
+int layernorm_launch(const char* fn, const void* x, void* out, void* aux, int64_t aux_stride, const void* weight, const void* bias,
+                     const void* scale1p, const void* shift, int64_t rows, int64_t dim, int64_t x_stride, int64_t out_stride, float eps,
+                     void* stream) {
+    constexpr bool FP8 = OUT == LN_FP8, MX4 = OUT == LN_MX4;
+    GF_CHECK_ARG(x && out && (OUT == LN_BF16 || aux), "%s: null %s", fn, FP8 ? "x/out8/scale" : MX4 ? "x/out4/scales" : "x/out");
+    if constexpr (OUT == LN_BF16) {
+        GF_CHECK_ARG(rows >= 0 && dim > 0 && dim % 8 == 0 && dim <= ROW_THREADS * ROW_NCH * 8,
+                     "%s: dim=%ld must be a multiple of 8 and <= %d", fn, (long)dim, ROW_THREADS * ROW_NCH * 8);
+    } else {
+        GF_CHECK_ARG(rows >= 0 && (dim == 5120 || dim == 4096 || dim == 1536),
+                     "%s: dim=%ld is not one of the wave-per-row widths (5120, 4096, 1536); use gf_layernorm_modulate + %s", fn, (long)dim,
+                     FP8 ? "gf_quant_fp8_rowscale" : "gf_quant_mxfp4");
+    }
+    if constexpr (MX4) {
+        GF_CHECK_ARG(x_stride % 8 == 0 && x_stride >= dim && out_stride % 4 == 0 && out_stride >= dim / 2 && aux_stride >= dim / 32,
+                     "%s: strides must be multiples of 8 (x) / 4 (out4) and cover the row", fn);
+    }
+    GF_CHECK_ARG((MX4 || (x_stride % 8 == 0 && out_stride % 8 == 0)) && gf_aligned16(x) && (((uintptr_t)out) & (MX4 ? 3u : FP8 ? 7u : 15u)) == 0,
+                 "%s: rows must be %s aligned", fn, MX4 ? "16-byte (x) / 4-byte (out4)" : FP8 ? "16-byte (x) / 8-byte (out8)" : "16-byte");
+    GF_CHECK_ARG((!weight || gf_aligned16(weight)) && (!bias || gf_aligned16(bias)) &&
+                     (!scale1p || gf_aligned16(scale1p)) && (!shift || gf_aligned16(shift)),
+                 "%s: vectors must be 16-byte aligned", fn);
+    if (rows == 0) return GF_OK;
+    const int mode = (!weight && !bias && !scale1p && !shift) ? 0 : (weight && bias && !scale1p && !shift) ? 1
+                     : (!weight && !bias && scale1p && shift) ? 2 : -1;
+    const u16* av = (const u16*)(mode == 1 ? weight : scale1p);
+    const u16* bv = (const u16*)(mode == 1 ? bias : shift);
+    const dim3 grid((unsigned)((rows + WROWS - 1) / WROWS)), block(64 * WROWS);
+    const hipStream_t s = (hipStream_t)stream;
+    const bool wave = ln_pick<10, 8, 3>(dim % 512 ? 0 : dim / 512, [&](auto nch) {
+        constexpr int NCH = decltype(nch)::value;
+        const bool specialised = ln_pick<0, 1, 2>(mode, [&](auto m) {
+            hipLaunchKernelGGL((layernorm_wave2_kernel<NCH, decltype(m)::value, FP8, MX4>), grid, block, 0, s, (const u16*)x, out,
+                               (float*)(FP8 ? aux : nullptr), av, bv, (long)rows, (long)x_stride, (long)out_stride, eps,
+                               (unsigned char*)(MX4 ? aux : nullptr), (long)aux_stride);
+        });
+        if (specialised) return;
+        if constexpr (FP8)
+            hipLaunchKernelGGL((layernorm_modulate_wave_kernel<NCH, OUT, float>), grid, block, 0, s, (const u16*)x, out, (float*)aux,
+                               (const u16*)weight, (const u16*)bias, (const u16*)scale1p, (const u16*)shift, (long)rows, (long)x_stride,
+                               (long)out_stride, eps, (unsigned char*)nullptr, 0L);
+        else
+            hipLaunchKernelGGL((layernorm_modulate_wave_kernel<NCH, OUT>), grid, block, 0, s, (const u16*)x, out, (const u16*)weight,
+                               (const u16*)bias, (const u16*)scale1p, (const u16*)shift, (long)rows, (long)x_stride, (long)out_stride,
+                               eps, (unsigned char*)aux, (long)aux_stride);
+    });
+    if constexpr (OUT == LN_BF16) {
+        if (!wave)
+            hipLaunchKernelGGL(layernorm_modulate_kernel, dim3((unsigned)rows), dim3(ROW_THREADS), 0, s, (const u16*)x, (u16*)out,
+                               (const u16*)weight, (const u16*)bias, (const u16*)scale1p, (const u16*)shift, (int)dim, (long)x_stride,
+                               (long)out_stride, eps);
+    }
+    GF_CHECK_LAUNCH(fn);
+    return GF_OK;
+}
+
+}  // namespace
+
 extern "C" GF_API int gf_layernorm_modulate(const void* x, void* out, const void* weight, const void* bias,
                                      const void* scale1p, const void* shift, int64_t rows, int64_t dim,
                                      int64_t x_stride, int64_t out_stride, float eps, void* stream) {
-    GF_CHECK_ARG(x && out, "gf_layernorm_modulate: null x/out");
-    GF_CHECK_ARG(rows >= 0 && dim > 0 && dim % 8 == 0 && dim <= ROW_THREADS * ROW_NCH * 8,
-                 "gf_layernorm_modulate: dim=%ld must be a multiple of 8 and <= %d", (long)dim,
-                 ROW_THREADS * ROW_NCH * 8);
-    GF_CHECK_ARG(x_stride % 8 == 0 && out_stride % 8 == 0 && gf_aligned16(x) && gf_aligned16(out),
-                 "gf_layernorm_modulate: rows must be 16-byte aligned");
-    GF_CHECK_ARG((!weight || gf_aligned16(weight)) && (!bias || gf_aligned16(bias)) &&
-                     (!scale1p || gf_aligned16(scale1p)) && (!shift || gf_aligned16(shift)),
-                 "gf_layernorm_modulate: vectors must be 16-byte aligned");
-    if (rows == 0) return GF_OK;
-    {   // the three operand sets of the DiT (plain, weight + bias, scale + shift) at the wave-per-row widths: the specialised kernel
-        const int mode = (!weight && !bias && !scale1p && !shift) ? 0 : (weight && bias && !scale1p && !shift) ? 1
-                         : (!weight && !bias && scale1p && shift) ? 2 : -1;
-        const void* av = mode == 1 ? weight : scale1p;
-        const void* bv = mode == 1 ? bias : shift;
-        const dim3 grid_((unsigned)((rows + WROWS - 1) / WROWS)), block_(64 * WROWS);
-#define GF_LN2(NCH, M)                                                                                                   \
-    if (dim == NCH * 512 && mode == M) {                                                                                 \
-        hipLaunchKernelGGL((layernorm_wave2_kernel<NCH, M, false>), grid_, block_, 0, (hipStream_t)stream, (const u16*)x, out,     \
-                           (float*)nullptr, (const u16*)av, (const u16*)bv, (long)rows, (long)x_stride, (long)out_stride, eps);     \
-        GF_CHECK_LAUNCH("gf_layernorm_modulate");                                                                        \
-        return GF_OK;                                                                                                    \
-    }
-        GF_LN2(10, 0) GF_LN2(10, 1) GF_LN2(10, 2) GF_LN2(8, 0) GF_LN2(8, 1) GF_LN2(8, 2) GF_LN2(3, 0) GF_LN2(3, 1) GF_LN2(3, 2)
-#undef GF_LN2
-    }
-#define GF_LN_WAVE(NCH)                                                                                                  \
-    if (dim == NCH * 512) {                                                                                              \
-        hipLaunchKernelGGL(layernorm_modulate_wave_kernel<NCH>, dim3((unsigned)((rows + WROWS - 1) / WROWS)),            \
-                           dim3(64 * WROWS), 0, (hipStream_t)stream, (const u16*)x, (u16*)out, (const u16*)weight,       \
-                           (const u16*)bias, (const u16*)scale1p, (const u16*)shift, (long)rows, (long)x_stride,        \
-                           (long)out_stride, eps);                                                                       \
-        GF_CHECK_LAUNCH("gf_layernorm_modulate");                                                                        \
-        return GF_OK;                                                                                                    \
-    }
-    GF_LN_WAVE(10) GF_LN_WAVE(8) GF_LN_WAVE(3)
-#undef GF_LN_WAVE
-    hipLaunchKernelGGL(layernorm_modulate_kernel, dim3((unsigned)rows), dim3(ROW_THREADS), 0,
-                       (hipStream_t)stream, (const u16*)x, (u16*)out, (const u16*)weight, (const u16*)bias,
-                       (const u16*)scale1p, (const u16*)shift, (int)dim, (long)x_stride, (long)out_stride, eps);
-    GF_CHECK_LAUNCH("gf_layernorm_modulate");
-    return GF_OK;
+    return layernorm_launch<LN_BF16>("gf_layernorm_modulate", x, out, nullptr, 0, weight, bias, scale1p, shift, rows, dim, x_stride,
+                                     out_stride, eps, stream);
 }
 
 extern "C" GF_API int gf_layernorm_modulate_fp8(const void* x, void* out8, float* scale, const void* weight, const void* bias,
                                                 const void* scale1p, const void* shift, int64_t rows, int64_t dim,
                                                 int64_t x_stride, int64_t out_stride, float eps, void* stream) {
-    GF_CHECK_ARG(x && out8 && scale, "gf_layernorm_modulate_fp8: null x/out8/scale");
-    GF_CHECK_ARG(rows >= 0 && (dim == 5120 || dim == 4096 || dim == 1536),
-                 "gf_layernorm_modulate_fp8: dim=%ld is not one of the wave-per-row widths (5120, 4096, 1536); use "
-                 "gf_layernorm_modulate + gf_quant_fp8_rowscale", (long)dim);
-    GF_CHECK_ARG(x_stride % 8 == 0 && out_stride % 8 == 0 && gf_aligned16(x) && (((uintptr_t)out8) & 7u) == 0,
-                 "gf_layernorm_modulate_fp8: rows must be 16-byte (x) / 8-byte (out8) aligned");
-    GF_CHECK_ARG((!weight || gf_aligned16(weight)) && (!bias || gf_aligned16(bias)) &&
-                     (!scale1p || gf_aligned16(scale1p)) && (!shift || gf_aligned16(shift)),
-                 "gf_layernorm_modulate_fp8: vectors must be 16-byte aligned");
-    if (rows == 0) return GF_OK;
-    {
-        const int mode = (!weight && !bias && !scale1p && !shift) ? 0 : (weight && bias && !scale1p && !shift) ? 1
-                         : (!weight && !bias && scale1p && shift) ? 2 : -1;
-        const void* av = mode == 1 ? weight : scale1p;
-        const void* bv = mode == 1 ? bias : shift;
-        const dim3 grid_((unsigned)((rows + WROWS - 1) / WROWS)), block_(64 * WROWS);
-#define GF_LN2(NCH, M)                                                                                                   \
-    if (dim == NCH * 512 && mode == M) {                                                                                 \
-        hipLaunchKernelGGL((layernorm_wave2_kernel<NCH, M, true>), grid_, block_, 0, (hipStream_t)stream, (const u16*)x, out8,     \
-                           scale, (const u16*)av, (const u16*)bv, (long)rows, (long)x_stride, (long)out_stride, eps);   \
-        GF_CHECK_LAUNCH("gf_layernorm_modulate_fp8");                                                                    \
-        return GF_OK;                                                                                                    \
-    }
-        GF_LN2(10, 0) GF_LN2(10, 1) GF_LN2(10, 2) GF_LN2(8, 0) GF_LN2(8, 1) GF_LN2(8, 2) GF_LN2(3, 0) GF_LN2(3, 1) GF_LN2(3, 2)
-#undef GF_LN2
-    }
-#define GF_LN8_WAVE(NCH)                                                                                                 \
-    if (dim == NCH * 512) {                                                                                              \
-        hipLaunchKernelGGL(layernorm_modulate_fp8_wave_kernel<NCH>, dim3((unsigned)((rows + WROWS - 1) / WROWS)),        \
-                           dim3(64 * WROWS), 0, (hipStream_t)stream, (const u16*)x, (unsigned char*)out8, scale,          \
-                           (const u16*)weight, (const u16*)bias, (const u16*)scale1p, (const u16*)shift, (long)rows,     \
-                           (long)x_stride, (long)out_stride, eps);                                                       \
-    }
-    GF_LN8_WAVE(10) GF_LN8_WAVE(8) GF_LN8_WAVE(3)
-#undef GF_LN8_WAVE
-    GF_CHECK_LAUNCH("gf_layernorm_modulate_fp8");
-    return GF_OK;
+    return layernorm_launch<LN_FP8>("gf_layernorm_modulate_fp8", x, out8, scale, 0, weight, bias, scale1p, shift, rows, dim, x_stride,
+                                    out_stride, eps, stream);
 }
 
 extern "C" GF_API int gf_layernorm_modulate_mxfp4(const void* x, void* out4, void* scales, const void* weight, const void* bias,
                                                   const void* scale1p, const void* shift, int64_t rows, int64_t dim, int64_t x_stride,
                                                   int64_t out_stride, int64_t scale_stride, float eps, void* stream) {
-    GF_CHECK_ARG(x && out4 && scales, "gf_layernorm_modulate_mxfp4: null x/out4/scales");
-    GF_CHECK_ARG(rows >= 0 && (dim == 5120 || dim == 4096 || dim == 1536),
-                 "gf_layernorm_modulate_mxfp4: dim=%ld is not one of the wave-per-row widths (5120, 4096, 1536); use "
-                 "gf_layernorm_modulate + gf_quant_mxfp4", (long)dim);
-    GF_CHECK_ARG(x_stride % 8 == 0 && x_stride >= dim && out_stride % 4 == 0 && out_stride >= dim / 2 && scale_stride >= dim / 32,
-                 "gf_layernorm_modulate_mxfp4: strides must be multiples of 8 (x) / 4 (out4) and cover the row");
-    GF_CHECK_ARG(gf_aligned16(x) && (((uintptr_t)out4) & 3u) == 0,
-                 "gf_layernorm_modulate_mxfp4: rows must be 16-byte (x) / 4-byte (out4) aligned");
-    GF_CHECK_ARG((!weight || gf_aligned16(weight)) && (!bias || gf_aligned16(bias)) &&
-                     (!scale1p || gf_aligned16(scale1p)) && (!shift || gf_aligned16(shift)),
-                 "gf_layernorm_modulate_mxfp4: vectors must be 16-byte aligned");
-    if (rows == 0) return GF_OK;
-    const dim3 grid_((unsigned)((rows + WROWS - 1) / WROWS)), block_(64 * WROWS);
-    {
-        const int mode = (!weight && !bias && !scale1p && !shift) ? 0 : (weight && bias && !scale1p && !shift) ? 1
-                         : (!weight && !bias && scale1p && shift) ? 2 : -1;
-        const void* av = mode == 1 ? weight : scale1p;
-        const void* bv = mode == 1 ? bias : shift;
-#define GF_LN2(NCH, M)                                                                                                   \
-    if (dim == NCH * 512 && mode == M) {                                                                                 \
-        hipLaunchKernelGGL((layernorm_wave2_kernel<NCH, M, false, true>), grid_, block_, 0, (hipStream_t)stream, (const u16*)x,    \
-                           out4, (float*)nullptr, (const u16*)av, (const u16*)bv, (long)rows, (long)x_stride, (long)out_stride,  \
-                           eps, (unsigned char*)scales, (long)scale_stride);                                             \
-        GF_CHECK_LAUNCH("gf_layernorm_modulate_mxfp4");                                                                  \
-        return GF_OK;                                                                                                    \
-    }
-        GF_LN2(10, 0) GF_LN2(10, 1) GF_LN2(10, 2) GF_LN2(8, 0) GF_LN2(8, 1) GF_LN2(8, 2) GF_LN2(3, 0) GF_LN2(3, 1) GF_LN2(3, 2)
-#undef GF_LN2
-    }
-#define GF_LN4_WAVE(NCH)                                                                                                 \
-    if (dim == NCH * 512) {                                                                                              \
-        hipLaunchKernelGGL((layernorm_modulate_wave_kernel<NCH, true>), grid_, block_, 0, (hipStream_t)stream, (const u16*)x,      \
-                           (u16*)out4, (const u16*)weight, (const u16*)bias, (const u16*)scale1p, (const u16*)shift, (long)rows, \
-                           (long)x_stride, (long)out_stride, eps, (unsigned char*)scales, (long)scale_stride);           \
-    }
-    GF_LN4_WAVE(10) GF_LN4_WAVE(8) GF_LN4_WAVE(3)
-#undef GF_LN4_WAVE
-    GF_CHECK_LAUNCH("gf_layernorm_modulate_mxfp4");
-    return GF_OK;
+    return layernorm_launch<LN_MX4>("gf_layernorm_modulate_mxfp4", x, out4, scales, scale_stride, weight, bias, scale1p, shift, rows,
+                                    dim, x_stride, out_stride, eps, stream);
 }
 
 extern "C" GF_API int gf_rmsnorm_rope(void* x, const void* weight, const float* cos_tab, const float* sin_tab,

@@ -155,73 +155,77 @@ def param_key(*tensors):
     return (_CACHE_EPOCH[0],) + tuple((id(t), str(t.device), t.data_ptr(), None if t.is_inference() else t._version) for t in tensors)
 
 
-class QuantizedInput:
-    """Row-quantised activation (e4m3 bytes + per-row scale) shared by the GEMMs that read the same input."""
+# A Linear's low-precision modes, the one that wins first: kind -> (the attribute of its weight copy, whose master's param_key is in
+# <attribute>_key; the ops quantiser of a weight; of an activation; the LayerNorm producing the activation), looked up at call time
+_QUANT = {"fp4": ("_gf_w4", "quant_mxfp4", "quant_mxfp4", "layernorm_modulate_mxfp4"),
+          "fp8": ("_gf_w8", "cast_fp8", "quant_fp8_rowscale", "layernorm_modulate_fp8")}
 
-    def __init__(self, x2=None, x8=None, scale=None):
-        self.x8, self.scale = ops.quant_fp8_rowscale(x2) if x2 is not None else (x8, scale)
+
+def precision(lin: nn.Module, kinds=tuple(_QUANT)) -> str:
+    """"fp4" | "fp8" | "bf16": the first of `kinds` the layer carries a weight copy of — what dit.linear runs it in."""
+    return next((k for k in kinds if getattr(lin, _QUANT[k][0], None) is not None), "bf16")
+
+
+def weight_copy(lin: nn.Linear, kind: str, enabled=None):
+    """The layer's copy of `kind`, quantised again if the bf16 master changed since (param_key), or None; `enabled`: make / remove it."""
+    attr, quantise = _QUANT[kind][:2]
+    copy = getattr(lin, attr, None)
+    if enabled is not None or (copy is not None and getattr(lin, attr + "_key") != param_key(lin.weight)):
+        copy = None if enabled is False else getattr(ops, quantise)(lin.weight.detach().contiguous())
+        setattr(lin, attr, copy)
+        setattr(lin, attr + "_key", None if copy is None else param_key(lin.weight))
+    return copy
+
+
+fp8_weight = functools.partial(weight_copy, kind="fp8")    # the layer's current e4m3 copy (enable_fp8), or None
+fp4_weight = functools.partial(weight_copy, kind="fp4")    # ... MXFP4 copy (enable_fp4) as (packed e2m1 codes, E8M0 scales), or None
+
+
+class QuantizedInput:
+    """A quantised activation shared by the GEMMs that read the same input: `kind` "fp8" — `data` e4m3 bytes, `scale` fp32 per row;
+    "fp4" — MXFP4, `data` packed e2m1 codes, `scale` E8M0 bytes (what ops.layernorm_modulate_mxfp4 / ops.gemm_mxfp4_q4 return)."""
+
+    def __init__(self, x2=None, data=None, scale=None, kind="fp8"):
+        self.kind = kind
+        self.data, self.scale = getattr(ops, _QUANT[kind][2])(x2) if x2 is not None else (data, scale)
 
     @classmethod
-    def layernorm(cls, x2, **kw):
-        """LayerNorm(+affine)(+modulate) of x2 delivered as an fp8_linear input (ops.layernorm_modulate_fp8)."""
-        return cls(None, *ops.layernorm_modulate_fp8(x2, **kw))
+    def layernorm(cls, x2, kind="fp8", **kw):
+        """LayerNorm(+affine)(+modulate) of x2 delivered as the input of a `kind` layer (ops.layernorm_modulate_fp8 / _mxfp4)."""
+        return cls(None, *getattr(ops, _QUANT[kind][3])(x2, **kw), kind=kind)
 
-    @property
-    def shape(self):
-        return self.x8.shape
-
-    @property
-    def is_cuda(self):
-        return self.x8.is_cuda
-
-
-def fp8_weight(lin: nn.Linear):
-    """The layer's current e4m3 weight copy (enable_fp8), or None for a bf16 layer."""
-    w8 = getattr(lin, "_gf_w8", None)
-    if w8 is not None and lin._gf_w8_key != param_key(lin.weight):          # the bf16 master changed since the cast: refresh the copy
-        w8 = lin._gf_w8 = ops.cast_fp8(lin.weight.detach().contiguous())
-        lin._gf_w8_key = param_key(lin.weight)
-    return w8
-
-
-def fp4_weight(lin: nn.Linear):
-    """The layer's current MXFP4 weight copy (enable_fp4) as (packed e2m1 codes, E8M0 scales), or None."""
-    w4 = getattr(lin, "_gf_w4", None)
-    if w4 is not None and lin._gf_w4_key != param_key(lin.weight):          # the bf16 master changed since the quantisation: refresh the copy
-        w4 = lin._gf_w4 = ops.quant_mxfp4(lin.weight.detach().contiguous())
-        lin._gf_w4_key = param_key(lin.weight)
-    return w4
+    shape = property(lambda self: self.data.shape)
+    is_cuda = property(lambda self: self.data.is_cuda)
 
 
 def linear(x2, lin: nn.Linear, epilogue=ops.EPI_BIAS, resid=None, gate=None, out=None):
-    """One nn.Linear on the MFMA GEMM.  If the layer carries an fp8 weight copy (enable_fp8) the reference's
-    fp8_linear contract is used (VRAM:115-151: per-row dynamic activation scale, unit weight scale, e4m3),
-    otherwise the bf16 kernel.  x2 may be a QuantizedInput to reuse one quantisation for several layers.
-    An MXFP4 weight copy (enable_fp4) wins over both: the bf16 input is quantised by ops.quant_mxfp4 and the product runs on
-    ops.gemm_mxfp4; a QuantizedInput (fp8) is refused there."""
-    w4 = fp4_weight(lin)
-    if w4 is not None:
-        if isinstance(x2, QuantizedInput):
-            raise GoalForceError("linear: an fp8 QuantizedInput was handed to an enable_fp4 layer, which quantises its own bf16 input")
-        x4, xs = ops.quant_mxfp4(x2)
-        return ops.gemm_mxfp4(x4, xs, w4[0], w4[1], lin.bias, epilogue=epilogue, resid=resid, gate=gate, out=out)
-    w8 = fp8_weight(lin)
-    if w8 is None:
-        return ops.gemm(x2, lin.weight, lin.bias, epilogue=epilogue, resid=resid, gate=gate, out=out)
-    q = x2 if isinstance(x2, QuantizedInput) else QuantizedInput(x2)
-    return ops.gemm_fp8(q.x8, q.scale, w8, lin.bias, epilogue=epilogue, resid=resid, gate=gate, out=out)
+    """One nn.Linear on the MFMA GEMM, in the layer's precision(): the bf16 kernel; the reference's fp8_linear contract (enable_fp8;
+    VRAM:115-151: per-row dynamic activation scale, unit weight scale, e4m3); ops.gemm_mxfp4 (enable_fp4).  A bf16 x2 is quantised here
+    for the layer; a QuantizedInput of the layer's kind reuses one quantisation for several layers, one of another kind is refused.
+    out=QuantizedInput (the class): an fp4 layer's result as the next one's input, quantised in the GEMM's epilogue (ops.gemm_mxfp4_q4)."""
+    kind, given = precision(lin), getattr(x2, "kind", "bf16")
+    w = lin.weight if kind == "bf16" else weight_copy(lin, kind)
+    if given not in ("bf16", kind):
+        raise GoalForceError(f"linear: an {given} QuantizedInput was handed to " + (
+            "a bf16 layer" if kind == "bf16" else f"an enable_{kind} layer, which quantises its own bf16 input"))
+    if out is QuantizedInput and kind != "fp4":
+        raise GoalForceError(f"linear: a QuantizedInput result is what one enable_fp4 layer hands the next; this layer runs in {kind}")
+    if kind == "bf16":
+        return ops.gemm(x2, w, lin.bias, epilogue=epilogue, resid=resid, gate=gate, out=out)
+    q = x2 if given == kind else QuantizedInput(x2, kind=kind)
+    if out is QuantizedInput:
+        return QuantizedInput(None, *ops.gemm_mxfp4_q4(q.data, q.scale, *w, lin.bias, epilogue=epilogue), kind="fp4")
+    gemm, w = (ops.gemm_mxfp4, w) if kind == "fp4" else (ops.gemm_fp8, (w,))
+    return gemm(q.data, q.scale, *w, lin.bias, epilogue=epilogue, resid=resid, gate=gate, out=out)
 
 
 def enable_fp8(module: nn.Module, enabled=True):
     """BASELINE config 5: every nn.Linear inside the DiT / ControlNet *blocks* runs the fp8_linear contract
     (the reference would set computation_dtype=float8_e4m3fn in enable_vram_management, VRAM:113).  Weights are
     cast once to OCP e4m3 (unit scale) and kept beside the bf16 master copy."""
-    for blk in module.modules():
-        if isinstance(blk, DiTBlock):
-            for lin in blk.modules():
-                if isinstance(lin, nn.Linear):
-                    lin._gf_w8 = ops.cast_fp8(lin.weight.detach().contiguous()) if enabled else None
-                    lin._gf_w8_key = param_key(lin.weight) if enabled else None
+    for blk in (m for m in module.modules() if isinstance(m, DiTBlock)):
+        for lin in (m for m in blk.modules() if isinstance(m, nn.Linear)):
+            weight_copy(lin, "fp8", bool(enabled))
     return module
 
 
@@ -254,8 +258,7 @@ def enable_fp4(module: nn.Module, enabled=True, layers=FP4_LAYERS):
             for lin in fp4_linears(blk, layers):
                 if enabled and lin.weight.shape[1] % 256:
                     raise GoalForceError(f"enable_fp4: a Linear with {lin.weight.shape[1]} input features: gf_gemm_mxfp4 needs a multiple of 256")
-                lin._gf_w4 = ops.quant_mxfp4(lin.weight.detach().contiguous()) if enabled else None
-                lin._gf_w4_key = param_key(lin.weight) if enabled else None
+                weight_copy(lin, "fp4", bool(enabled))
     return module
 
 
@@ -299,12 +302,10 @@ def enable_sparse_attention(module: nn.Module, pattern, dense_blocks: int = 0):
 
 def refuse_training(block: "DiTBlock"):
     """What training.DiTBlockFn refuses of a block's switches, before its forward runs."""
-    if any(getattr(m, "_gf_w8", None) is not None for m in block.modules()):
-        # the backward recomputes the block on the bf16 kernels: an fp8 forward would not be the function differentiated
-        raise GoalForceError("training through an enable_fp8 block is refused: call enable_fp8(module, False) first")
-    if any(getattr(m, "_gf_w4", None) is not None for m in block.modules()):
-        # the same reason: the backward differentiates the bf16 block
-        raise GoalForceError("training through an enable_fp4 block is refused: call enable_fp4(module, False) first")
+    # the backward recomputes the block on the bf16 kernels: an fp8 / fp4 forward would not be the function differentiated
+    for kind in ("fp8", "fp4"):      # (in this order, whichever of the two wins on a layer that carries both)
+        if any(precision(m, (kind,)) == kind for m in block.modules()):
+            raise GoalForceError(f"training through an enable_{kind} block is refused: call enable_{kind}(module, False) first")
     if getattr(block.self_attn, "_gf_sage", False):
         # no backward exists for the sage backend (nor in the sageattention package): the backward would differentiate another function
         raise GoalForceError("training through a block with enable_sage_attention is refused: call enable_sage_attention(module, False) first")
@@ -457,8 +458,8 @@ class SelfAttention(nn.Module):
         keep["wide"] also the three projections ("qp", "kp" before their norm, "v").  `dense`: a block switched by
         enable_sparse_attention attends densely in this call (pipe.sparse_dense_steps)."""
         attn = self.attention_backend(rope, x2.shape[0], sp, keep, dense)
-        fp8 = getattr(self.q, "_gf_w8", None) is not None
-        xin = (x2 if isinstance(x2, QuantizedInput) else QuantizedInput(x2)) if fp8 else x2      # one quantisation for the three projections
+        fp8 = precision(self.q) == "fp8"         # then: one quantisation for the three projections
+        xin = (x2 if isinstance(x2, QuantizedInput) else QuantizedInput(x2)) if fp8 else x2
         q_rot = q_rotation(rope, self.head_dim, ops.option("attn_q_prescale"))
         if keep is not None:
             return self._attend_keep(xin, rope, q_rot, keep, sp)
@@ -488,7 +489,7 @@ class SelfAttention(nn.Module):
         if not xin.is_cuda or w.shape[0] < 512 or (fp8 and w.shape[1] % 128) or not ops.vt32_ok(xin.shape[0], self.num_heads, self.head_dim):
             return None
         if fp8:
-            return ops.linear_vt32_fp8(xin.x8, xin.scale, fp8_weight(self.v), self.v.bias)
+            return ops.linear_vt32_fp8(xin.data, xin.scale, fp8_weight(self.v), self.v.bias)
         return ops.linear_vt32(xin, w, self.v.bias)
 
     def _attend_head_parallel(self, xin, rope, q_rot, sp, backend):
@@ -550,7 +551,7 @@ class CrossAttention(nn.Module):
             if ctx2.shape[0] - n >= 2 and n + 1 < ops.VT_MIN_KV:      # (the multiplicity form exists for short key sequences only)
                 m = ctx2.shape[0] - n
                 ctx2 = ctx2[: n + 1]
-        cin = QuantizedInput(ctx2) if getattr(self.k, "_gf_w8", None) is not None else ctx2
+        cin = QuantizedInput(ctx2) if precision(self.k) == "fp8" else ctx2
         k, v = linear(cin, self.k), linear(cin, self.v)
         ops.rmsnorm_rope(k, self.norm_k.weight, None, None, self.head_dim, self.norm_k.eps)
         return k, v, m
@@ -574,7 +575,7 @@ class CrossAttention(nn.Module):
         2-head test models), ops.options(fold_cross_o) on."""
         if not ops.option("fold_cross_o") or torch.is_grad_enabled() or len(kv) < 3 or kv[2] == 1 or self.head_dim != 128:
             return False
-        if getattr(self.o, "_gf_w8", None) is not None or getattr(self.o, "_gf_w4", None) is not None:
+        if precision(self.o) != "bf16":
             return False
         n = kv[0].shape[0]
         k = self.num_heads * self.fold_pad(n)          # the projection GEMM's K: a multiple of 64 (gf_gemm_bf16)
@@ -633,12 +634,15 @@ class DiTBlock(nn.Module):
         self.modulation = nn.Parameter(torch.randn(1, 6, dim) / dim ** 0.5)
         self.gate = GateModule()
 
-    def _normed(self, x2, fp8: bool, out, **kw):
-        """LayerNorm(+affine)(+modulate) of x2 as the input of the linears that follow: under fp8 the normalised row goes straight
-        to e4m3 + scale_a (never to HBM as bf16), else into the bf16 buffer `out` (None: a new one) — which is returned."""
-        if fp8:
-            return QuantizedInput.layernorm(x2, eps=self.eps, **kw)
-        return ops.layernorm_modulate(x2, eps=self.eps, out=out, **kw)
+    _fused_linear = staticmethod(linear)    # the fused fp4 FFN's: a substitute installed as dit.linear sees the layers handed bf16, as ever
+
+    def _normed(self, x2, reader: nn.Linear, out, **kw):
+        """LayerNorm(+affine)(+modulate) of x2 as the input of `reader`: for an fp8 layer, and an fp4 one under ops.options(fp4_fused), a
+        QuantizedInput (the row never goes to HBM as bf16), else the bf16 buffer `out` (None: a new one) — which is returned."""
+        kind = precision(reader)
+        if kind == "bf16" or (kind == "fp4" and not ops.option("fp4_fused")):
+            return ops.layernorm_modulate(x2, eps=self.eps, out=out, **kw)
+        return QuantizedInput.layernorm(x2, kind, eps=self.eps, **kw)
 
     def forward(self, x, context, t_mod, freqs, context_kv=None, out=None, sp=None, keep=None, self_attn_memo=None,
                 fold_pad_keys=True, pad_n=None, dense_attn=False):
@@ -653,10 +657,8 @@ class DiTBlock(nn.Module):
         rope = _as_rope(freqs, x.device)
         # rows: shift_msa, 1+scale_msa, gate_msa, shift_mlp, 1+scale_mlp, gate_mlp   (DIT:218-219, 64-65)
         mod = ops.modulation(self.modulation, t_mod.contiguous(), onep_mask=0b010010)
-        # config 5: every Linear of the block on the fp8_linear contract — all of them or none (enable_fp8).  Read from a layer
-        # enable_fp4 never takes; an fp4 layer wants its input in bf16 whatever this flag says
-        fp8 = getattr(self.self_attn.q, "_gf_w8", None) is not None
-        fp4_ffn = getattr(self.ffn[0], "_gf_w4", None) is not None
+        # config 5: every Linear of the block on the fp8_linear contract, all or none (enable_fp8); read from a layer enable_fp4 never takes
+        fp8 = precision(self.self_attn.q) == "fp8"
         if self_attn_memo is not None and "x" in self_attn_memo:
             x_new = self_attn_memo.pop("x")
             ev = self_attn_memo.pop("ev", None)
@@ -667,7 +669,7 @@ class DiTBlock(nn.Module):
                 x_new = out.copy_(x_new)
             h = None if fp8 else torch.empty_like(x2)
         else:
-            h = self._normed(x2, fp8, None, scale1p=mod[1], shift=mod[0])                              # DIT:225
+            h = self._normed(x2, self.self_attn.q, None, scale1p=mod[1], shift=mod[0])                 # DIT:225
             a = self.self_attn.attend(h, rope, sp, keep, dense=dense_attn)
             x_new = out if out is not None else torch.empty_like(x2)
             linear(a, self.self_attn.o, epilogue=ops.EPI_BIAS_GATE_RESID, resid=x2, gate=mod[2], out=x_new)   # DIT:226
@@ -678,7 +680,8 @@ class DiTBlock(nn.Module):
                 if x_new.is_cuda:
                     self_attn_memo["ev"] = torch.cuda.Event()
                     self_attn_memo["ev"].record(torch.cuda.current_stream(x_new.device))
-        h = self._normed(x_new, fp8, h, weight=self.norm3.weight, bias=self.norm3.bias)
+        buf = None if fp8 else h        # the bf16 buffer of the first LayerNorm serves the other two
+        h = self._normed(x_new, self.cross_attn.q, buf, weight=self.norm3.weight, bias=self.norm3.bias)
         if context_kv is None:
             context_kv = self.cross_attn.context_kv(_tokens2d(context), fold=fold_pad_keys and keep is None, pad_n=pad_n)
         ca = self.cross_attn
@@ -691,19 +694,15 @@ class DiTBlock(nn.Module):
             linear(a, ca.o, epilogue=ops.EPI_BIAS_RESID, resid=x_new, out=x_new)                        # DIT:227
         if keep is not None and keep.get("wide"):
             keep["x2b"] = x_new.clone()
-        if fp4_ffn and ops.option("fp4_fused"):
-            # the FFN under enable_fp4 in three launches: the LayerNorm and the GELU GEMM quantise what they hold in registers, so
-            # neither bf16 intermediate ([S, D], [S, F]) exists; the bits of the five-launch route below (ops.options(fp4_fused=False))
-            w0, w2 = fp4_weight(self.ffn[0]), fp4_weight(self.ffn[2])
-            assert w2 is not None, "enable_fp4 names ffn[0] and ffn[2] together"
-            h4, hs = ops.layernorm_modulate_mxfp4(x_new, scale1p=mod[4], shift=mod[3], eps=self.eps)      # DIT:228
-            f4, fs = ops.gemm_mxfp4_q4(h4, hs, w0[0], w0[1], self.ffn[0].bias, epilogue=ops.EPI_BIAS_GELU_TANH)
-            ops.gemm_mxfp4(f4, fs, w2[0], w2[1], self.ffn[2].bias, epilogue=ops.EPI_BIAS_GATE_RESID, resid=x_new, gate=mod[5],
-                           out=x_new)                                                                     # DIT:229
-            return x_new.view(x.shape)
-        h = self._normed(x_new, fp8 and not fp4_ffn, None if fp8 else h, scale1p=mod[4], shift=mod[3])  # DIT:228
-        f1 = linear(h, self.ffn[0], epilogue=ops.EPI_BIAS_GELU_TANH)
-        linear(f1, self.ffn[2], epilogue=ops.EPI_BIAS_GATE_RESID, resid=x_new, gate=mod[5], out=x_new)  # DIT:229
+        # the FFN under enable_fp4 and ops.options(fp4_fused) in three launches: the LayerNorm and the GELU GEMM quantise what they hold
+        # in registers, so neither bf16 intermediate ([S, D], [S, F]) exists; the bits of the five-launch route (fp4_fused=False)
+        fused = precision(self.ffn[0]) == "fp4" and ops.option("fp4_fused")
+        ffn_linear = self._fused_linear if fused else linear
+        if fused:       # (enable_fp4 names ffn[0] and ffn[2] together; this route brings both copies up to date before its LayerNorm)
+            fp4_weight(self.ffn[0]), fp4_weight(self.ffn[2])
+        h = self._normed(x_new, self.ffn[0], buf, scale1p=mod[4], shift=mod[3])                          # DIT:228
+        f1 = ffn_linear(h, self.ffn[0], epilogue=ops.EPI_BIAS_GELU_TANH, out=QuantizedInput if fused else None)
+        ffn_linear(f1, self.ffn[2], epilogue=ops.EPI_BIAS_GATE_RESID, resid=x_new, gate=mod[5], out=x_new)  # DIT:229
         return x_new.view(x.shape)
 
 

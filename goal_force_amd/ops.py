@@ -171,17 +171,31 @@ def modulation(param, t, onep_mask: int):
     return out
 
 
+LN_QUANT_WIDTHS = (5120, 4096, 1536)   # the wave-per-row widths: the only ones gf_layernorm_modulate_fp8 / _mxfp4 take
+LN_FP8_WIDTHS = LN_QUANT_WIDTHS        # (its name from before the MXFP4 producer)
+
+
+def _layernorm_operands(op, x, weight, bias, scale1p, shift, out=None, widths=None):
+    """The checks of the three LayerNorm wrappers, in `op`'s words -> (x as [rows, dim] rows, rows, dim, row stride); None — before
+    the vectors are looked at — for a row length outside `widths`, where the caller runs the two-kernel pair and layernorm_modulate
+    does the refusing."""
+    _req(x, f"{op}.x")
+    xv, rows, dim, xs = _rows2d(x, f"{op}.x")
+    if widths is not None and dim not in widths:
+        return None
+    if out is not None:
+        _rows2d(out, f"{op}.out")
+    for name, vec in (("weight", weight), ("bias", bias), ("scale1p", scale1p), ("shift", shift)):
+        _vec(vec, f"{op}.{name}", dim)
+    return xv, rows, dim, xs
+
+
 def layernorm_modulate(x, weight=None, bias=None, scale1p=None, shift=None, eps=1e-6, out=None):
     """LayerNorm(+affine)(+modulate) — gf_layernorm_modulate."""
-    _req(x, "layernorm_modulate.x")
-    xv, rows, dim, xs = _rows2d(x, "layernorm_modulate.x")
+    xv, rows, dim, xs = _layernorm_operands("layernorm_modulate", x, weight, bias, scale1p, shift, out)
     if out is None:
         out = torch.empty(x.shape, dtype=_BF16, device=x.device)
     ov, _, _, os_ = _rows2d(out, "layernorm_modulate.out")
-    _vec(weight, "layernorm_modulate.weight", dim)
-    _vec(bias, "layernorm_modulate.bias", dim)
-    _vec(scale1p, "layernorm_modulate.scale1p", dim)
-    _vec(shift, "layernorm_modulate.shift", dim)
     _lib.check(_lib.load().gf_layernorm_modulate(_ptr(xv), _ptr(ov), _ptr(weight), _ptr(bias), _ptr(scale1p),
                                                  _ptr(shift), rows, dim, xs, os_, float(eps), _stream(x)),
                "gf_layernorm_modulate")
@@ -247,23 +261,29 @@ def rope_apply(x, cos, sin, head_dim):
     return out
 
 
+def _gemm_result_operands(op, M, N, out, resid, gate, bias):
+    """What a GEMM wrapper takes besides its two factors, checked in `op`'s words (`out` [M, N] is the caller's or new) ->
+    (out as rows, ldc, resid as rows or None, ldr)."""
+    ov, Mo, No, ldc = _rows2d(out, f"{op}.out")
+    if (Mo, No) != (M, N):
+        raise GoalForceError(f"{op}.out: expected [{M}, {N}], got [{Mo}, {No}]")
+    ldr = 0
+    if resid is not None:
+        _req(resid, f"{op}.resid")
+        resid, Mr, Nr, ldr = _rows2d(resid, f"{op}.resid")
+        if (Mr, Nr) != (M, N):
+            raise GoalForceError(f"{op}.resid: expected [{M}, {N}], got [{Mr}, {Nr}]")
+    _vec(gate, f"{op}.gate", N)
+    _vec(bias, f"{op}.bias", N)
+    return ov, ldc, resid, ldr
+
+
 def _gemm(a, w, row_scale, bias, epilogue, resid, gate, out):
-    """gemm (row_scale None) and gemm_fp8: one set of checks, then gf_gemm_bf16 / gf_gemm_fp8 (which takes the row scales after ldw).
-    The names in its errors are constants (the wrappers run thousands of times per denoise step)."""
+    """gemm (row_scale None) and gemm_fp8: one set of checks, then gf_gemm_bf16 / gf_gemm_fp8 (which takes the row scales after ldw)."""
     av, M, K, lda, N, ldw = _linear_operands(a, w, row_scale)
     if out is None:
         out = torch.empty(a.shape[:-1] + (N,), dtype=_BF16, device=a.device)
-    ov, Mo, No, ldc = _rows2d(out, "gemm[_fp8].out")
-    if (Mo, No) != (M, N):
-        raise GoalForceError(f"gemm[_fp8].out: expected [{M}, {N}], got [{Mo}, {No}]")
-    ldr = 0
-    if resid is not None:
-        _req(resid, "gemm[_fp8].resid")
-        resid, Mr, Nr, ldr = _rows2d(resid, "gemm[_fp8].resid")
-        if (Mr, Nr) != (M, N):
-            raise GoalForceError(f"gemm[_fp8].resid: expected [{M}, {N}], got [{Mr}, {Nr}]")
-    _vec(gate, "gemm[_fp8].gate", N)
-    _vec(bias, "gemm[_fp8].bias", N)
+    ov, ldc, resid, ldr = _gemm_result_operands("gemm[_fp8]", M, N, out, resid, gate, bias)
     lib = _lib.load()
     fn, scale = (lib.gf_gemm_bf16, ()) if row_scale is None else (lib.gf_gemm_fp8, (_ptr(row_scale),))
     with _timed(PROFILE_GEMM, M, N, K, int(epilogue)):
@@ -1516,21 +1536,14 @@ def quant_fp8_rowscale(x):
     return out, scale
 
 
-LN_FP8_WIDTHS = (5120, 4096, 1536)     # gf_layernorm_modulate_fp8's wave-per-row widths
-
-
 def layernorm_modulate_fp8(x, weight=None, bias=None, scale1p=None, shift=None, eps=1e-6):
     """LayerNorm(+affine)(+modulate) straight into the fp8_linear input format: (x8 [M,K] float8_e4m3fn, scale_a [M] fp32) —
     gf_layernorm_modulate_fp8 at the DiT widths (the bf16 row never reaches HBM), elsewhere the two kernels it fuses; the same
     bits either way."""
-    _req(x, "layernorm_modulate_fp8.x")
-    xv, rows, dim, xs = _rows2d(x, "layernorm_modulate_fp8.x")
-    if dim not in LN_FP8_WIDTHS:
+    operands = _layernorm_operands("layernorm_modulate_fp8", x, weight, bias, scale1p, shift, widths=LN_QUANT_WIDTHS)
+    if operands is None:
         return quant_fp8_rowscale(layernorm_modulate(x, weight=weight, bias=bias, scale1p=scale1p, shift=shift, eps=eps))
-    _vec(weight, "layernorm_modulate_fp8.weight", dim)
-    _vec(bias, "layernorm_modulate_fp8.bias", dim)
-    _vec(scale1p, "layernorm_modulate_fp8.scale1p", dim)
-    _vec(shift, "layernorm_modulate_fp8.shift", dim)
+    xv, rows, dim, xs = operands
     out = torch.empty((rows, dim), dtype=_FP8, device=x.device)
     scale = torch.empty((rows,), dtype=torch.float32, device=x.device)
     _lib.check(_lib.load().gf_layernorm_modulate_fp8(_ptr(xv), _ptr(out), _ptr(scale), _ptr(weight), _ptr(bias), _ptr(scale1p),
@@ -1576,14 +1589,10 @@ def layernorm_modulate_mxfp4(x, weight=None, bias=None, scale1p=None, shift=None
     """LayerNorm(+affine)(+modulate) straight into the fp4 Linear's input format: (x4 [M,K/2] uint8 packed e2m1, scale [M,K/32] uint8
     E8M0) — gf_layernorm_modulate_mxfp4 at the DiT widths (the bf16 row never reaches HBM), elsewhere the two kernels it fuses; the
     same bits either way."""
-    _req(x, "layernorm_modulate_mxfp4.x")
-    xv, rows, dim, xs = _rows2d(x, "layernorm_modulate_mxfp4.x")
-    if dim not in LN_FP8_WIDTHS:
+    operands = _layernorm_operands("layernorm_modulate_mxfp4", x, weight, bias, scale1p, shift, widths=LN_QUANT_WIDTHS)
+    if operands is None:
         return quant_mxfp4(layernorm_modulate(x, weight=weight, bias=bias, scale1p=scale1p, shift=shift, eps=eps))
-    _vec(weight, "layernorm_modulate_mxfp4.weight", dim)
-    _vec(bias, "layernorm_modulate_mxfp4.bias", dim)
-    _vec(scale1p, "layernorm_modulate_mxfp4.scale1p", dim)
-    _vec(shift, "layernorm_modulate_mxfp4.shift", dim)
+    xv, rows, dim, xs = operands
     out = torch.empty((rows, dim // 2), dtype=torch.uint8, device=x.device)
     scale = torch.empty((rows, dim // 32), dtype=torch.uint8, device=x.device)
     _lib.check(_lib.load().gf_layernorm_modulate_mxfp4(_ptr(xv), _ptr(out), _ptr(scale), _ptr(weight), _ptr(bias), _ptr(scale1p),
@@ -1631,21 +1640,11 @@ def gemm_mxfp4_q4(a4, a_scale, w4, w_scale, bias=None, epilogue=EPI_BIAS):
 
 def gemm_mxfp4(a4, a_scale, w4, w_scale, bias=None, epilogue=EPI_BIAS, resid=None, gate=None, out=None):
     """out[M,N] = epilogue(bf16(deq(a4, a_scale) @ deq(w4, w_scale)^T + bias)) — gf_gemm_mxfp4.  a4 [M,K/2] / w4 [N,K/2] uint8 packed
-    e2m1, a_scale [M,K/32] / w_scale [N,K/32] uint8 E8M0 (ops.quant_mxfp4); K % 256 == 0.  The checks and their words are _gemm's."""
+    e2m1, a_scale [M,K/32] / w_scale [N,K/32] uint8 E8M0 (ops.quant_mxfp4); K % 256 == 0.  out / resid / gate / bias as in _gemm."""
     M, N, K, ldw = _mxfp4_operands(a4, a_scale, w4, w_scale)
     if out is None:
         out = torch.empty((M, N), dtype=_BF16, device=a4.device)
-    ov, Mo, No, ldc = _rows2d(out, "gemm_mxfp4.out")
-    if (Mo, No) != (M, N):
-        raise GoalForceError(f"gemm_mxfp4.out: expected [{M}, {N}], got [{Mo}, {No}]")
-    ldr = 0
-    if resid is not None:
-        _req(resid, "gemm_mxfp4.resid")
-        resid, Mr, Nr, ldr = _rows2d(resid, "gemm_mxfp4.resid")
-        if (Mr, Nr) != (M, N):
-            raise GoalForceError(f"gemm_mxfp4.resid: expected [{M}, {N}], got [{Mr}, {Nr}]")
-    _vec(gate, "gemm_mxfp4.gate", N)
-    _vec(bias, "gemm_mxfp4.bias", N)
+    ov, ldc, resid, ldr = _gemm_result_operands("gemm_mxfp4", M, N, out, resid, gate, bias)
     if M == 0:                       # nothing to compute (an empty tensor has no address to hand over)
         return out
     with _timed(PROFILE_GEMM, M, N, K, int(epilogue)):

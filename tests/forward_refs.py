@@ -180,7 +180,7 @@ def ln_vectors(dim, generator, subset):
 
 
 LN_GENERAL = (8, 264, 2048, 8192)      # layernorm_modulate_kernel: 264 one ragged pass, 2048 two chunks per thread, 8192 the limit
-LN_WAVE = (1536, 4096, 5120)           # layernorm_wave2_kernel for DIT_SETS, layernorm_modulate_wave_kernel for every other set
+LN_WAVE = (1536, 4096, 5120)           # layernorm_wave2_kernel for DIT_SETS, layernorm_modulate_wave_kernel<NCH, OUT> for every other set
 ROWS = (1, 13)                         # 13: a ragged last workgroup of the wave kernels (4 rows each)
 
 

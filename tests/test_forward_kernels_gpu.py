@@ -11,9 +11,9 @@ input and are run on all 65 536 bit patterns.
 Which case reaches which kernel:
   layernorm_modulate_kernel (128 threads per row)         widths 8 / 264 / 2048 / 8192 of test_layernorm_every_path
   layernorm_wave2_kernel<NCH, MODE, false>                widths 1536 / 4096 / 5120 with the sets plain, weight+bias, scale1p+shift
-  layernorm_modulate_wave_kernel<NCH>                     width 5120 with the 13 other operand sets (the partial sets; the general
+  layernorm_modulate_wave_kernel<NCH, LN_BF16>            width 5120 with the 13 other operand sets (the partial sets; the general
                                                           kernel gets all 16 at width 264)
-  layernorm_modulate_fp8_wave_kernel<NCH>                 test_layernorm_fp8_partial_operand_sets (every set but the three above)
+  layernorm_modulate_wave_kernel<NCH, LN_FP8>             test_layernorm_fp8_partial_operand_sets (every set but the three above)
   layernorm_wave2_kernel<NCH, MODE, true>                 the same test's three DiT sets
   rmsnorm_rope_kernel                                     widths 8 / 264 / 2048 / 8192 of test_rmsnorm_rope_every_path
   rmsnorm_rope_wave_kernel<NCH, 0 | 1>                    widths 1536 / 4096 / 5120 without a table | head_dim 128, 64, 8

@@ -5,7 +5,10 @@ reached before it.  tests/golden/self_attn_dispatch.json was recorded by this mo
 dispatch was cut into named steps (`python tests/test_self_attn_dispatch_gpu.py --write tests/golden/self_attn_dispatch.json`, on
 an MI355X); the tests assert that the code reproduces it exactly.  The wrappers are recorded with their arguments bound to the
 wrapper's signature, defaults filled in, so `f(q, k, v, n, scale=s)` and `f(q, k, v, n, vt=None, scale=s)` — the same launch — are the
-same entry.  Every weight and input has a CPU generator of its own, seeded from its name: no case depends on another."""
+same entry.  Every weight and input has a CPU generator of its own, seeded from its name: no case depends on another.
+The `fp4` cases (enable_fp4 on the FFN and / or the o projections, fused and unfused, the memo half, a weight edited under a
+stale copy, the refusals) were recorded the same way on the commit BEFORE a layer's precision got one record in dit.py; each
+switches fp4 on before the recorder is installed and off again, with every copy current, when it is done."""
 import hashlib
 import inspect
 import itertools
@@ -25,6 +28,7 @@ DIM, HEADS, FFN = 512, 4, 1024
 GRIDS = {"long": (6, 16, 24), "short": (3, 4, 6)}
 WRAPPERS = ("gemm", "gemm_fp8", "quant_fp8_rowscale", "layernorm_modulate", "layernorm_modulate_fp8", "rmsnorm_rope", "linear_vt32",
             "linear_vt32_fp8", "flash_attn", "flash_attn_lse", "flash_attn_sparse", "sage_attn", "cast_fp8",
+            "gemm_mxfp4", "gemm_mxfp4_q4", "quant_mxfp4", "layernorm_modulate_mxfp4",
             "modulation", "cross_probs", "cross_fold_table")        # (the last three: DiTBlock.forward's other producers, for the identities)
 _DTYPES = {torch.bfloat16: "bf16", torch.float32: "f32", torch.uint8: "u8", torch.int8: "i8", torch.int32: "i32",
            getattr(torch, "float8_e4m3fn", None): "e4m3"}
@@ -132,6 +136,11 @@ CASES = ["attend-" + "-".join(c) for c in itertools.product(LINEARS, BACKENDS, S
 CASES += [f"attend-option-{o}" for o in OPTIONS]                                   # each switched OFF on the plain bf16 long case
 CASES += [f"blockfn-{kind}-{level}" for kind in ("fp8", "sage", "sparse") for level in ("none", "attn")]
 CASES += [f"block-{lin}-{memo}" for lin in LINEARS for memo in ("nomemo", "memo")]  # DiTBlock.forward, first and second call
+# enable_fp4 on top of either block: one forward per layer set and FFN route; the memo half; a weight edited under its copy (two
+# forwards: the first refreshes the copy, once; the second finds it current); what is refused by name before the first wrapper
+CASES += [f"block-{lin}-fp4{layers}-{route}" for lin in LINEARS for layers in ("ffn", "o", "ffn+o") for route in ("fused", "unfused")]
+CASES += ["block-fp8-fp4ffn+o-fused-memo", "block-fp8-stale", "block-bf16-fp4ffn-stale"]
+CASES += ["linear-fp8input-fp4o", "blockfn-fp4-none", "blockfn-fp4-attn", "enablefp4-q", "enablefp4-k128"]
 
 
 class Env:
@@ -170,8 +179,9 @@ class Env:
         for n, p in blk.named_parameters():
             rec.name(p, n)
         for n, m in blk.named_modules():
-            if getattr(m, "_gf_w8", None) is not None:
-                rec.name(m._gf_w8, n + ".w8")
+            for kind in ("w8", "w4"):                                   # (an fp4 copy is (codes, scales): `<layer>.w4.0` / `.w4.1`)
+                if getattr(m, "_gf_" + kind, None) is not None:
+                    rec.name(getattr(m, "_gf_" + kind), f"{n}.{kind}")
 
 
 def _pattern(kind):
@@ -220,28 +230,46 @@ def _blockfn(env, rec, kind, level):
     return {"out": rec.describe(out), "sha256": _sha(out)}          # (not reached: every one of these is refused)
 
 
-def _block(env, rec, lin, memo):
+def _block(env, rec, lin, *flags, calls=("first", "second")):
+    """DiTBlock.forward once per name in `calls`.  flags: memo | nomemo; unfused (ops.options(fp4_fused=False)); stale (ffn[0]'s
+    weight doubled in place under its current copy before the first call: run_case halves it again)."""
+    from goal_force_amd import ops
     blk = env.blocks[lin]
-    memo = {} if memo == "memo" else None
+    memo = {} if "memo" in flags else None
     res = {}
-    for call in ("first", "second"):
-        out = blk(env.x["long"][None], env.ctx[None], env.t_mod, env.rope["long"], self_attn_memo=memo)
-        res[call] = {"out": rec.describe(out), "sha256": _sha(out), "calls_so_far": len(rec.entries),
-                     "memo": None if memo is None else sorted(memo)}
+    if "stale" in flags:
+        blk.ffn[0].weight.mul_(2.0)
+    with ops.options(fp4_fused="unfused" not in flags):
+        for call in calls:
+            out = blk(env.x["long"][None], env.ctx[None], env.t_mod, env.rope["long"], self_attn_memo=memo)
+            res[call] = {"out": rec.describe(out), "sha256": _sha(out), "calls_so_far": len(rec.entries),
+                         "memo": None if memo is None else sorted(memo)}
     return res
+
+
+def _fp4_layers(kind, rest):
+    """The enable_fp4 layer names a case switches on before its recording starts (() for a case without fp4)."""
+    if kind == "block":
+        return tuple(n for f in rest if f.startswith("fp4") for n in f[3:].split("+"))
+    return {("blockfn", "fp4"): ("ffn", "o"), ("linear", "fp8input"): ("o",)}.get((kind, rest[0]), ())
 
 
 def run_case(env, case, mp):
     """One case -> its record: {"calls": [entries], ...result} or {"refused": text, "calls_before": n}."""
     from goal_force_amd import ops
     from goal_force_amd._lib import GoalForceError
+    from goal_force_amd import dit
     kind, *rest = case.split("-")
+    g = rest[-1] if kind == "attend" and rest[0] != "option" else "long"
+    lin = "fp8" if rest[0] == "fp8" else "bf16"
+    blk, fp4 = env.blocks[lin], _fp4_layers(kind, rest)
+    if fp4:                                         # before the recorder: the case is what runs on the switched block
+        dit.enable_fp4(blk, layers=fp4)
+    x8 = dit.QuantizedInput(env.x["short"]) if kind == "linear" else None
     rec = Recorder(mp)
     for w in WRAPPERS:
         rec.wrap(ops, w, w)
-    g = rest[-1] if kind == "attend" and rest[0] != "option" else "long"
-    lin = "fp8" if rest[0] == "fp8" else "bf16"
-    env.name_inputs(rec, env.blocks[lin], g)
+    env.name_inputs(rec, blk, g)
     try:
         with torch.no_grad():
             if kind == "attend" and rest[0] == "option":
@@ -251,11 +279,26 @@ def run_case(env, case, mp):
                 res = _attend(env, rec, *rest)
             elif kind == "blockfn":
                 res = _blockfn(env, rec, *rest)
+            elif kind == "linear":
+                res = {"out": rec.describe(dit.linear(x8, blk.self_attn.o))}        # (not reached: refused)
+            elif kind == "enablefp4":
+                res = {"out": rec.describe(dit.enable_fp4(dit.DiTBlock(False, 128, 1, 128) if rest[0] == "k128" else blk,
+                                                          layers=("ffn", "o") if rest[0] == "k128" else (rest[0],)))}
             else:
-                res = _block(env, rec, *rest)
+                two = any(f in ("memo", "nomemo", "stale") for f in rest)
+                res = _block(env, rec, *rest, calls=("first", "second") if two else ("first",))
+        record = json.loads(json.dumps({"calls": rec.entries, **res}))
     except GoalForceError as e:
-        return {"refused": str(e), "calls_before": len(rec.entries)}
-    return json.loads(json.dumps({"calls": rec.entries, **res}))
+        record = {"refused": str(e), "calls_before": len(rec.entries)}
+    finally:
+        mp.undo()                                   # the recording is over: what follows leaves the block as the case found it
+        if fp4:
+            dit.enable_fp4(blk, False, layers=fp4)
+        if "stale" in rest:
+            with torch.no_grad():
+                blk.ffn[0].weight.mul_(0.5)         # exact: the bf16 master is the seeded one again
+            dit.fp8_weight(blk.ffn[0])              # and the copy current (fp4's left with enable_fp4(False))
+    return record
 
 
 @pytest.fixture(scope="module")
@@ -271,6 +314,13 @@ def recorded():
 
 def test_the_fixture_holds_exactly_the_cases(recorded):
     assert sorted(recorded) == sorted(CASES)
+
+
+def test_a_stale_copy_is_refreshed_once_and_only_on_the_first_call(recorded):
+    for case, op in (("block-fp8-stale", "cast_fp8"), ("block-bf16-fp4ffn-stale", "quant_mxfp4")):
+        calls, first = recorded[case]["calls"], recorded[case]["first"]["calls_so_far"]
+        at = [i for i, c in enumerate(calls) if c["op"] == op and any(str(v).endswith(":ffn.0.weight") for v in c["args"].values())]
+        assert len(at) == 1 and at[0] < first, (case, at, first)
 
 
 @pytest.mark.parametrize("case", CASES)
