@@ -45,18 +45,19 @@ def training_loss(dit_sd, cn_sd, cfg, n_cn, input_latents, noise, context, y, co
     return loss * weights[tid]
 
 
-def loss_and_grads(dit_sd, cn_sd, cfg, n_cn, inputs, timestep_id, dtype=torch.float32, num_steps=1000, shift=5.0):
+def loss_and_grads(dit_sd, cn_sd, cfg, n_cn, inputs, timestep_id, dtype=torch.float32, num_steps=1000, shift=5.0, timestep_dtype=None):
     """Loss and d(loss)/d(ControlNet parameter) for every entry of cn_sd; inputs: dict with input_latents, noise, context,
-    y, control.  The DiT state dict is frozen, as in training (only `pipe.controlnet.*` is trainable, GF:97-117)."""
+    y, control.  The DiT state dict is frozen, as in training (only `pipe.controlnet.*` is trainable, GF:97-117).
+    timestep_dtype: as training_loss's (a yardstick in a wider dtype of a bf16 run passes torch.bfloat16)."""
     with torch.enable_grad():
-        return _loss_and_grads(dit_sd, cn_sd, cfg, n_cn, inputs, timestep_id, dtype, num_steps, shift)
+        return _loss_and_grads(dit_sd, cn_sd, cfg, n_cn, inputs, timestep_id, dtype, num_steps, shift, timestep_dtype)
 
 
-def _loss_and_grads(dit_sd, cn_sd, cfg, n_cn, inputs, timestep_id, dtype, num_steps, shift):
+def _loss_and_grads(dit_sd, cn_sd, cfg, n_cn, inputs, timestep_id, dtype, num_steps, shift, timestep_dtype=None):
     dsd = {k: v.detach().to(dtype) for k, v in dit_sd.items()}
     csd = {k: v.detach().to(dtype).requires_grad_(True) for k, v in cn_sd.items()}
     inp = {k: v.to(dtype) for k, v in inputs.items()}
     loss = training_loss(dsd, csd, cfg, n_cn, inp["input_latents"], inp["noise"], inp["context"], inp["y"], inp["control"],
-                         timestep_id, num_steps, shift)
+                         timestep_id, num_steps, shift, timestep_dtype=timestep_dtype)
     loss.backward()
     return loss.detach(), {k: v.grad for k, v in csd.items()}

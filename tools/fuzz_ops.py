@@ -10,7 +10,8 @@ against the bounds of tests/attention_fwd_refs.py, `--only gemmpin` (opt-in) the
 of tests/gemm_refs.py, `--only vaepin` (opt-in) the VAE's convolution kernels against the plain fp64 convolution of tests/vae_refs.py
 through the same bars, `--only crossfold` (opt-in) the folded cross-attention's two kernels through the raw C ABI against the bars of
 tests/cross_fold_refs.py, `--only sagepin` (opt-in) the SageAttention kernels on the exact classes and through the two bars of
-tests/sage_refs.py."""
+tests/sage_refs.py, `--only tape` (opt-in) the training tape of one block (training.DiTBlockFn.backward) at random token grids, context
+lengths, keep levels and parameter subsets through the row statistic of tests/tape_refs.py."""
 import argparse
 import math
 import os
@@ -697,10 +698,54 @@ def case_sagepin(rnd, g):
     return desc + " | " + R.describe(j), err, 1.0
 
 
-CASES = {"gemmpin": case_gemmpin, "vaepin": case_vaepin, "gemm": case_gemm, "attn": case_attn, "rows": case_rows, "cfg": case_cfg, "attnbwd": case_attnbwd, "fp8": case_fp8,
+def case_tape(rnd, g):
+    """training.DiTBlockFn.backward held as tests/test_tape_gpu.py holds it (helper: tests/tape_refs.py): a block at the tiny widths on a
+    random token grid, context length, keep level, q pre-scale and subset of trainable parameters against fp64 autograd of the oracle;
+    err = the worst row-statistic ratio over its group's ROW_BAR (inf for a non-zero value in a slice whose reference is identically zero,
+    or a .grad on a parameter nobody asked for); bar 1."""
+    for p in (os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests", "golden")):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    import gen_inputs as gi
+    import tape_refs as T
+    from goal_force_amd import training
+    from goal_force_amd.dit import DiTBlock, RopeTable, precompute_freqs_cis_3d
+    grid = (rnd.randrange(1, 4), rnd.randrange(1, 9), rnd.randrange(1, 14))
+    case = dict(name="fuzz", cfg="TINY", grid=grid, ctx_len=rnd.choice([1, 7, 63, 64, 65, rnd.randrange(1, 130)]),
+                prescale=rnd.random() < 0.7, seed=rnd.randrange(1 << 20))
+    level = rnd.choice(["none", "attn", "wide"])
+    subset = tuple(T.PARAM_NAMES) if rnd.random() < 0.4 else tuple(n for n in T.PARAM_NAMES if rnd.random() < 0.3)
+    cfg, sd, x, ctx, t_mod, dout = T.case_inputs(case, gi)
+    ref = T.with_dx(*T.block_grads_ref(cfg, sd, x, ctx, t_mod, dout, grid))
+    c0 = T.with_dx(*T.block_chain(cfg, sd, x, ctx, t_mod, dout, grid, 0, case["prescale"]))
+    blk = DiTBlock(False, cfg["dim"], cfg["num_heads"], cfg["ffn_dim"], cfg["eps"])
+    blk.load_state_dict(sd, strict=True)
+    blk = blk.to(BF).cuda()
+    for n, p_ in blk.named_parameters():
+        p_.requires_grad_(n in subset)
+    rope = RopeTable.from_grid(precompute_freqs_cis_3d(cfg["dim"] // cfg["num_heads"]), *grid, "cuda")
+    old = training.set_keep_level(level)
+    try:
+        with torch.enable_grad(), ops.options(attn_q_prescale=case["prescale"]):
+            xc = x.cuda().requires_grad_(True)
+            training.block_forward(blk, xc, ctx.cuda(), t_mod.cuda(), rope).backward(dout.cuda())
+    finally:
+        training.set_keep_level(old)
+    named = dict(blk.named_parameters())
+    stray = [n for n in T.PARAM_NAMES if (named[n].grad is not None) != (n in subset)]
+    got = {n: named[n].grad.cpu() for n in subset if named[n].grad is not None}
+    got["dx"] = xc.grad.cpu()
+    stats = T.measure(got, c0, ref)
+    err = max([s["worst"] / T.ROW_BAR[T.group(n)] for n, s in stats.items()] + [math.inf if (stray or any(s["zero_bad"] for s in stats.values())) else 0.0])
+    where = max(stats.items(), key=lambda kv: kv[1]["worst"] / T.ROW_BAR[T.group(kv[0])])
+    return (f"tape grid={grid} ctx={case['ctx_len']} keep={level} prescale={case['prescale']} params={len(subset)} | worst {where[0]} {where[1]['where']} "
+            f"{where[1]['worst']:.3f}"), err, 1.0
+
+
+CASES = {"tape": case_tape, "gemmpin": case_gemmpin, "vaepin": case_vaepin, "gemm": case_gemm, "attn": case_attn, "rows": case_rows, "cfg": case_cfg, "attnbwd": case_attnbwd, "fp8": case_fp8,
          "batched": case_batched, "misc": case_misc, "bwdrows": case_bwdrows, "fwdrows": case_fwdrows, "attnfwd": case_attnfwd, "crossfold": case_crossfold,
          "sagepin": case_sagepin}
-OPT_IN = ("fwdrows", "attnfwd", "gemmpin", "vaepin", "crossfold", "sagepin")       # run with --only alone (bwdrows is in the default sweep): the default sweep, and the suite's run of it, stays what it was
+OPT_IN = ("fwdrows", "attnfwd", "gemmpin", "vaepin", "crossfold", "sagepin", "tape")     # run with --only alone (bwdrows is in the default sweep): the default sweep, and the suite's run of it, stays what it was
 
 
 def main():
