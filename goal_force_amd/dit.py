@@ -17,7 +17,7 @@ from typing import Optional, Tuple
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import lora, ops
 from ._lib import GoalForceError
 
 
@@ -202,8 +202,27 @@ def linear(x2, lin: nn.Linear, epilogue=ops.EPI_BIAS, resid=None, gate=None, out
     """One nn.Linear on the MFMA GEMM, in the layer's precision(): the bf16 kernel; the reference's fp8_linear contract (enable_fp8;
     VRAM:115-151: per-row dynamic activation scale, unit weight scale, e4m3); ops.gemm_mxfp4 (enable_fp4).  A bf16 x2 is quantised here
     for the layer; a QuantizedInput of the layer's kind reuses one quantisation for several layers, one of another kind is refused.
-    out=QuantizedInput (the class): an fp4 layer's result as the next one's input, quantised in the GEMM's epilogue (ops.gemm_mxfp4_q4)."""
+    out=QuantizedInput (the class): an fp4 layer's result as the next one's input, quantised in the GEMM's epilogue (ops.gemm_mxfp4_q4).
+    A bf16 layer with attached LoRA adapters of non-zero strength (lora.attach) runs its GEMM with EPI_BIAS, then per adapter
+    ops.gemm for t = x down^T and ops.lora_up, the last one with the caller's epilogue, resid, gate and out."""
     kind, given = precision(lin), getattr(x2, "kind", "bf16")
+    adapters = lora.live(lin)
+    if adapters:
+        if kind != "bf16":
+            raise GoalForceError(f"linear: an attached LoRA adapter ({adapters[0].name!r}) on an enable_{kind} layer is refused: use the "
+                                 "merged form (pipe.load_lora) with quantised layers, or lora.detach first")
+        if given != "bf16" or out is QuantizedInput:
+            raise GoalForceError(f"linear: a QuantizedInput was handed to or asked of a layer with an attached LoRA adapter "
+                                 f"({adapters[0].name!r}): attached adapters run on bf16 activations only")
+        y = ops.gemm(x2, lin.weight, lin.bias)
+        for i, ad in enumerate(adapters):
+            ad.on(y.device)
+            t = ops.gemm(x2, ad.down)
+            if i + 1 < len(adapters):
+                ops.lora_up(y, t, ad.up, ad.alpha, out=y)
+            else:
+                y = ops.lora_up(y, t, ad.up, ad.alpha, epilogue=epilogue, resid=resid, gate=gate, out=y if out is None else out)
+        return y
     w = lin.weight if kind == "bf16" else weight_copy(lin, kind)
     if given not in ("bf16", kind):
         raise GoalForceError(f"linear: an {given} QuantizedInput was handed to " + (
@@ -306,6 +325,10 @@ def refuse_training(block: "DiTBlock"):
     for kind in ("fp8", "fp4"):      # (in this order, whichever of the two wins on a layer that carries both)
         if any(precision(m, (kind,)) == kind for m in block.modules()):
             raise GoalForceError(f"training through an enable_{kind} block is refused: call enable_{kind}(module, False) first")
+    for name, m in block.named_modules():
+        if lora.live(m):      # the backward differentiates the plain layer: an attached adapter would be in the forward only
+            raise GoalForceError(f"training through a block with a live LoRA adapter ({name}: {lora.live(m)[0].name!r}) is refused: "
+                                 "call lora.detach(module) or lora.set_strength(module, 0) first")
     if getattr(block.self_attn, "_gf_sage", False):
         # no backward exists for the sage backend (nor in the sageattention package): the backward would differentiate another function
         raise GoalForceError("training through a block with enable_sage_attention is refused: call enable_sage_attention(module, False) first")
@@ -486,6 +509,8 @@ class SelfAttention(nn.Module):
         transpose, one pass over V less; config 5: gf_linear_vt32_fp8).  -> the V^T operand, or None where the plain projection runs."""
         w = self.v.weight
         fp8 = isinstance(xin, QuantizedInput)
+        if lora.live(self.v):          # an attached adapter goes through dit.linear: the plain projection runs
+            return None
         if not xin.is_cuda or w.shape[0] < 512 or (fp8 and w.shape[1] % 128) or not ops.vt32_ok(xin.shape[0], self.num_heads, self.head_dim):
             return None
         if fp8:
@@ -575,7 +600,7 @@ class CrossAttention(nn.Module):
         2-head test models), ops.options(fold_cross_o) on."""
         if not ops.option("fold_cross_o") or torch.is_grad_enabled() or len(kv) < 3 or kv[2] == 1 or self.head_dim != 128:
             return False
-        if precision(self.o) != "bf16":
+        if precision(self.o) != "bf16" or lora.live(self.o):      # (an attached adapter on o: the unfolded path, through dit.linear)
             return False
         n = kv[0].shape[0]
         k = self.num_heads * self.fold_pad(n)          # the projection GEMM's K: a multiple of 64 (gf_gemm_bf16)
@@ -704,6 +729,9 @@ class DiTBlock(nn.Module):
         f1 = ffn_linear(h, self.ffn[0], epilogue=ops.EPI_BIAS_GELU_TANH, out=QuantizedInput if fused else None)
         ffn_linear(f1, self.ffn[2], epilogue=ops.EPI_BIAS_GATE_RESID, resid=x_new, gate=mod[5], out=x_new)  # DIT:229
         return x_new.view(x.shape)
+
+
+LORA_HOSTS = (DiTBlock, SelfAttention, CrossAttention)     # the modules whose Linears all run through linear(): what lora.attach takes
 
 
 class Head(nn.Module):

@@ -48,15 +48,22 @@ import torch
 
 from . import ops
 from ._lib import GoalForceError
+from . import dit as _dit
 from .dit import WanModel, pad_run
 from .temporal_tiler import TemporalTiler_BCTHW, check_window
 
 
 class ContextCache:
     """Per (expert, prompt) memo of text_embedding(context) and the cross-attention K/V of every block
-    of the DiT and of its ControlNet (GF:1447, DIT:177-179 are recomputed each call in the reference)."""
+    of the DiT and of its ControlNet (GF:1447, DIT:177-179 are recomputed each call in the reference).  A memo kept
+    across a change the weights' keys cannot show (dit.invalidate_caches: a merged or an attached LoRA adapter) empties itself on
+    its next use."""
 
     def __init__(self):
+        self.reset()
+
+    def reset(self):
+        self.epoch = _dit._CACHE_EPOCH[0]
         self.ctx = None
         self.pad_n = None       # dit.pad_run(ctx): where the run of identical padded rows starts — detected once, used by every block
         self.dit_kv = {}
@@ -159,6 +166,8 @@ def model_fn_wan_video(
     t, t_mod = dit.time_embed(timestep)
 
     # Text embedding (GF:1447)
+    if context_cache is not None and context_cache.epoch != _dit._CACHE_EPOCH[0]:
+        context_cache.reset()
     if context_cache is not None and context_cache.ctx is not None:
         ctx, pad_n = context_cache.ctx, context_cache.pad_n
     else:

@@ -16,7 +16,7 @@ from ._lib import (EPI_BIAS, EPI_BIAS_GATE_RESID, EPI_BIAS_GELU_TANH, EPI_BIAS_M
 
 __all__ = [
     "modulation", "layernorm_modulate", "rmsnorm_rope", "gate_residual", "gemm", "flash_attn", "flash_attn_sparse", "BlockMap", "block_means", "block_means_coherence", "block_map_scores", "block_map_select", "block_map_from_qk", "patchify_im2col", "unpatchify",
-    "cfg_euler_step", "act", "add", "sub", "rel_l1", "force_map",
+    "cfg_euler_step", "act", "add", "sub", "rel_l1", "force_map", "lora_merge", "lora_up",
     "EPI_BIAS", "EPI_BIAS_GELU_TANH", "EPI_BIAS_GATE_RESID", "EPI_BIAS_RESID", "EPI_BIAS_SILU", "EPI_BIAS_MUL",
 ]
 
@@ -295,6 +295,61 @@ def _gemm(a, w, row_scale, bias, epilogue, resid, gate, out):
 def gemm(a, w, bias=None, epilogue=EPI_BIAS, resid=None, gate=None, out=None):
     """out[M,N] = epilogue(a[M,K] @ w[N,K]^T + bias) — gf_gemm_bf16."""
     return _gemm(a, w, None, bias, epilogue, resid, gate, out)
+
+
+LORA_MAX_RANK = 256
+
+
+def _lora_scale(op, name, value):
+    value = float(value)
+    if not math.isfinite(value):
+        raise GoalForceError(f"{op}: {name} must be finite, got {value}")
+    return value
+
+
+def lora_merge(w, up, down, alpha=1.0):
+    """In place: w[n,k] <- bf16(w + bf16(fp32(alpha) * bf16(sum_j up[n,j] down[j,k]))) — gf_lora_merge (the reference's
+    GeneralLoRALoader.load on one weight).  w [n_out, k_in], up [n_out, r], down [r, k_in] bf16 with contiguous rows (row strides go
+    to the kernel); 1 <= r <= 256.  The weight's version is bumped, so every copy keyed on it (dit.param_key) is rebuilt; an
+    inference tensor has no version: call dit.invalidate_caches() (lora.load does)."""
+    for name, t in (("w", w), ("up", up), ("down", down)):
+        _mat(t, f"lora_merge.{name}")
+        if t.device != w.device:
+            raise GoalForceError(f"lora_merge.{name}: lives on {t.device}, w on {w.device}")
+    (n_out, k_in), r = w.shape, up.shape[1]
+    if up.shape[0] != n_out or tuple(down.shape) != (r, k_in):
+        raise GoalForceError(f"lora_merge: w is [{n_out}, {k_in}]: expected up [{n_out}, r] and down [r, {k_in}], got {tuple(up.shape)} "
+                             f"and {tuple(down.shape)}")
+    if not 1 <= r <= LORA_MAX_RANK:
+        raise GoalForceError(f"lora_merge: rank {r}: expected 1 <= r <= {LORA_MAX_RANK}")
+    alpha = _lora_scale("lora_merge", "alpha", alpha)
+    _lib.check(_lib.load().gf_lora_merge(_ptr(w), w.stride(0), _ptr(up), up.stride(0), _ptr(down), down.stride(0), n_out, k_in, r,
+                                         alpha, _stream(w)), "gf_lora_merge")
+    # the kernel wrote through the raw pointer: tell torch, as adamw_step does
+    if not w.is_inference():
+        torch.autograd.graph.increment_version(w)
+    return w
+
+
+def lora_up(y0, t, up, scale, epilogue=EPI_BIAS, resid=None, gate=None, out=None):
+    """out[M,N] = epilogue(bf16(y0 + bf16(fp32(scale) * bf16(t[M,R] @ up[N,R]^T))), resid, gate) — gf_lora_up: one attached adapter on
+    a layer's output y0 = bf16(acc + bias), t = gemm(x, down_pad); R a multiple of 32, <= 256, up zero beyond the true rank.  `out`
+    may be y0 itself (None: a new tensor) or resid."""
+    _req(y0, "lora_up.y0")
+    yv, M, N, ldy = _rows2d(y0, "lora_up.y0")
+    tv, R = _rows_like(t, "lora_up.t", M, t.shape[-1]), t.shape[-1]
+    Nu, ld_up = _weight(up, "lora_up.up", R)
+    if Nu != N:
+        raise GoalForceError(f"lora_up.up: expected [{N}, {R}], got {tuple(up.shape)}")
+    if R % 32 or not 32 <= R <= LORA_MAX_RANK:
+        raise GoalForceError(f"lora_up: padded rank {R}: expected a multiple of 32 in 32..{LORA_MAX_RANK}")
+    scale = _lora_scale("lora_up", "scale", scale)
+    if out is None:
+        out = torch.empty(y0.shape, dtype=_BF16, device=y0.device)
+    ov, ldo, resid, ldr = _gemm_result_operands("lora_up", M, N, out, resid, gate, None)
+    _lib.check(_lib.load().gf_lora_up(_ptr(yv), ldy, _ptr(tv[0]), tv[1], _ptr(up), ld_up, _ptr(ov), ldo, M, N, R, scale, int(epilogue),
+                                      _ptr(resid), ldr, _ptr(gate), _stream(y0)), "gf_lora_up")
+    return out
 
 
 VT_MIN_KV = 2048   # key sequences at least this long go through the pre-transposed-V kernel (kernel 3)

@@ -166,6 +166,14 @@ class WanVideoPipeline(torch.nn.Module):
         sd = load_state_dict(path, torch_dtype=torch_dtype)
         module.load_state_dict({k.replace("pipe.controlnet.", "", 1): v for k, v in sd.items()}, strict=True)
 
+    def load_lora(self, module, path, alpha=1):
+        """GF:171-174 — `GeneralLoRALoader.load`: every `lora_A` / `lora_B` pair of the file (or of a state dict given in its place)
+        that names a Linear of `module` is merged into that weight in place, W <- bf16(W + bf16(alpha bf16(B A))) on the device
+        (lora.load, gf_lora_merge).  Irreversible and stacking, as there; the reversible per-call form is lora.attach."""
+        from . import lora
+        sd = path if isinstance(path, dict) else load_state_dict(path, torch_dtype=self.torch_dtype, device="cpu")
+        return lora.load(module, sd, alpha=alpha)
+
     def training_loss(self, **inputs):
         """GF:180-193 — same keyword inputs as the reference (`input_latents`, `noise`, `context`, `y`,
         `control_signal_video_latents`, optional `max_timestep_boundary` / `min_timestep_boundary`); returns the loss with

@@ -568,6 +568,29 @@ GF_API int gf_window_finalize(void* value, const void* weight, int64_t C, int64_
 GF_API int gf_modulate(const void* x, void* out, const void* scale, const void* shift, int64_t rows, int64_t dim,
                        int64_t x_stride, int64_t out_stride, void* stream);
 
+/* ------------------------------------------------------------------------
+ * LoRA adapters (gf_lora.hip).  Replaces GeneralLoRALoader.load (diffsynth/lora/__init__.py; GF:171-174) and peft's unmerged
+ * forward.  Both sum the rank in fp32 — chunks of 32 rank columns in ascending order, one v_mfma_f32_16x16x32_bf16 per chunk and
+ * output element (four per wave: its four accumulator fragments), the rank zero-padded to a multiple of 32 inside the kernel — and
+ * round to bf16 only after the last product.  A shape of more than 2^31 tiles of 64 x 64 is refused.
+ *
+ * gf_lora_merge — in place, W [n_out, ldw] bf16:
+ *     W[n,k] <- bf16( W[n,k] + bf16( alpha * bf16( sum_j up[n,j] * down[j,k] ) ) )
+ * the reference's three bf16 roundings (torch.mm, the scalar multiply by fp32(alpha), the add).  up [n_out, ld_up], down
+ * [rank, ld_down] bf16 with any row pitch that covers the row; 1 <= rank <= 256; alpha finite (0 still runs the chain).
+ * k_in % 8 == 0, ldw % 8 == 0, W 16-byte aligned.  Every refusal leaves W untouched.
+ *
+ * gf_lora_up — one attached adapter on a layer's output y0 = bf16(acc + bias) [M, ldy], t = bf16(x down^T) [M, ldt]:
+ *     out[m,n] = epi( bf16( y0[m,n] + bf16( scale * bf16( sum_j t[m,j] * up[n,j] ) ) ), resid, gate )
+ * with epi = gf_epilogue as gf_gemm_bf16 applies it to bf16(acc + bias).  up [N, ld_up] with columns true rank .. rank_pad - 1 zero;
+ * rank_pad a multiple of 32, <= 256; N % 8 == 0; every leading dimension a multiple of 8; 16-byte aligned bases.  out may alias
+ * y0 or resid.  resid / ldr / gate as gf_gemm_bf16. */
+GF_API int gf_lora_merge(void* W, int64_t ldw, const void* up, int64_t ld_up, const void* down, int64_t ld_down, int64_t n_out,
+                         int64_t k_in, int64_t rank, float alpha, void* stream);
+GF_API int gf_lora_up(const void* y0, int64_t ldy, const void* t, int64_t ldt, const void* up, int64_t ld_up, void* out, int64_t ldo,
+                      int64_t M, int64_t N, int64_t rank_pad, float scale, int epilogue, const void* resid, int64_t ldr,
+                      const void* gate, void* stream);
+
 /* ---- Canny-edge control signal (ControlSignalDataset_CannyEdge._generate_control_video, src/goal_force/unified_dataset.py:559-578;
  * the reference calls cv2 / controlnet_aux per frame on the host — absent here: OpenCV's published algorithm restated, "parity unpinned").
  * All images are uint8 [frames, H, W, 3] (HWC), all tables device arrays built by goal_force_amd/canny.py.
