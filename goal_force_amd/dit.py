@@ -326,8 +326,10 @@ def refuse_training(block: "DiTBlock"):
         if any(precision(m, (kind,)) == kind for m in block.modules()):
             raise GoalForceError(f"training through an enable_{kind} block is refused: call enable_{kind}(module, False) first")
     for name, m in block.named_modules():
-        if lora.live(m):      # the backward differentiates the plain layer: an attached adapter would be in the forward only
-            raise GoalForceError(f"training through a block with a live LoRA adapter ({name}: {lora.live(m)[0].name!r}) is refused: "
+        # a frozen attached adapter would be in the forward only; one made by lora.add_trainable is differentiated (training.DiTBlockFn)
+        frozen = [ad for ad in lora.live(m) if not ad.trainable]
+        if frozen:
+            raise GoalForceError(f"training through a block with a live LoRA adapter ({name}: {frozen[0].name!r}) is refused: "
                                  "call lora.detach(module) or lora.set_strength(module, 0) first")
     if getattr(block.self_attn, "_gf_sage", False):
         # no backward exists for the sage backend (nor in the sageattention package): the backward would differentiate another function

@@ -9,6 +9,12 @@
   peft's unmerged forward, result + lora_B(lora_A(x)) * scaling, per call (ops.gemm for x down^T, ops.lora_up).  The masters are
   never written; detached or at strength 0 the layer runs its single launch again, bit for bit.  bf16 layers only.
 
+* `add_trainable(module, target_modules, rank, alpha, name)` restates `add_lora_to_model` (src/goal_force/utils.py:450-459: peft's
+  LoraConfig + inject_adapter_in_model): a TRAINABLE adapter beside every Linear peft's rule matches, `lora_A` kaiming-uniform,
+  `lora_B` zero, registered under peft's parameter names.  dit.linear runs it exactly as an attached one; training.DiTBlockFn
+  differentiates it (ops.lora_grad).  `trainable_state_dict` / `load_trainable_state` are the checkpoint's two directions
+  (`mapping_lora_state_dict` + `load_state_dict(strict=False)`, utils.py:462-470, 577-583).
+
 Every refusal names the key or the module and comes before the first weight is touched.  The kohya spelling (`lora_up` /
 `lora_down` / `.alpha`) is not what the reference's loader reads: such a file matches nothing and 0 updates are reported, as there.
 """
@@ -115,6 +121,7 @@ def load(module: nn.Module, state_dict, alpha=1.0):
 class Adapter:
     """One attached adapter of one Linear: `down` [rank_pad, in] and `up` [out, rank_pad] bf16, zero beyond the true rank."""
     __slots__ = ("name", "alpha", "rank", "down", "up")
+    trainable = False
 
     def __init__(self, name, alpha, up, down, device):
         r = up.shape[1]
@@ -148,26 +155,36 @@ def _changed():
     dit.invalidate_caches()          # no ContextCache entry or fold table outlives the change
 
 
+def _hosted(module):
+    """What dit.linear runs: the Linears of the DiT / ControlNet blocks.  The embeddings and the head launch their GEMMs themselves
+    and would never look at an adapter."""
+    from . import dit
+    return {id(lin) for m in module.modules() if isinstance(m, dit.LORA_HOSTS) for lin in m.modules() if isinstance(lin, nn.Linear)}
+
+
+def _check_host(what, mod_name, lin, hosted, own_linears, name):
+    """The layers that take an adapter beside them (attached or trainable): bf16 Linears of the blocks, one adapter per name."""
+    from . import dit
+    if id(lin) not in hosted and not own_linears:
+        raise GoalForceError(f"{what}: {mod_name!r} is not a Linear of a DiT block (q / k / v / o, ffn.0, ffn.2), the layers an "
+                             "attached adapter runs on: use the merged form (pipe.load_lora) for it")
+    kind = dit.precision(lin)
+    if kind != "bf16":
+        raise GoalForceError(f"{what}: {mod_name!r} carries an enable_{kind} weight copy: attached adapters run on bf16 layers "
+                             "only (use the merged form, pipe.load_lora, with quantised layers)")
+    if any(ad.name == name for ad in adapters(lin)):
+        raise GoalForceError(f"{what}: {mod_name!r} already carries an adapter named {name!r}: detach it first or choose another name")
+
+
 def attach(module: nn.Module, state_dict, alpha=1.0, name="default", own_linears=False):
     """Attach every matching adapter of `state_dict` beside its Linear under `name`, at strength `alpha`.  Returns the count.
     `own_linears`: the caller runs the matched layers through dit.linear itself (a benchmark's bare nn.Linear), so layers outside
     the DiT blocks are taken too."""
-    from . import dit
     a = _alpha(alpha, "lora.attach")
     todo = plan(module, state_dict, "lora.attach")
-    # what dit.linear runs: the Linears of the DiT / ControlNet blocks.  The embeddings and the head launch their GEMMs themselves
-    # and would never look at an adapter
-    hosted = {id(lin) for m in module.modules() if isinstance(m, dit.LORA_HOSTS) for lin in m.modules() if isinstance(lin, nn.Linear)}
+    hosted = _hosted(module)
     for mod_name, lin, up, down in todo:
-        if id(lin) not in hosted and not own_linears:
-            raise GoalForceError(f"lora.attach: {mod_name!r} is not a Linear of a DiT block (q / k / v / o, ffn.0, ffn.2), the layers an "
-                                 "attached adapter runs on: use the merged form (pipe.load_lora) for it")
-        kind = dit.precision(lin)
-        if kind != "bf16":
-            raise GoalForceError(f"lora.attach: {mod_name!r} carries an enable_{kind} weight copy: attached adapters run on bf16 layers "
-                                 "only (use the merged form, pipe.load_lora, with quantised layers)")
-        if any(ad.name == name for ad in adapters(lin)):
-            raise GoalForceError(f"lora.attach: {mod_name!r} already carries an adapter named {name!r}: detach it first or choose another name")
+        _check_host("lora.attach", mod_name, lin, hosted, own_linears, name)
     for mod_name, lin, up, down in todo:
         ads = list(adapters(lin))
         ads.append(Adapter(name, a, up, down, lin.weight.device))
@@ -190,6 +207,9 @@ def detach(module: nn.Module, name=None):
     for lin, hit in list(_named(module, name)):
         n += len(hit)
         rest = [ad for ad in lin._gf_lora if not any(ad is h for h in hit)]
+        for ad in hit:
+            if ad.trainable:
+                ad.unregister(lin)
         if rest:
             lin._gf_lora = rest
         else:
@@ -210,3 +230,146 @@ def set_strength(module: nn.Module, alpha, name=None):
     if n:
         _changed()
     return n
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# trainable adapters
+class _Weight(nn.Module):
+    """`<linear>.lora_A.<name>` / `<linear>.lora_B.<name>`: holds `.weight`, so named_parameters() spells peft's names."""
+
+    def __init__(self, weight):
+        super().__init__()
+        self.weight = nn.Parameter(weight)
+
+
+class TrainableAdapter:
+    """One trainable adapter of one Linear.  The parameters ARE the operands the kernels read: `lora_A.<name>.weight` [rank_pad, in]
+    and `lora_B.<name>.weight` [out, rank_pad], bf16, zero beyond the true rank.  The padding has zero value and zero gradient
+    (its rows of t, dt are zero), so AdamW keeps it zero, an optimiser step needs no repack, and the true-rank tensors are slices
+    (trainable_state_dict).  `alpha` is the scaling lora_alpha / r that multiplies the update."""
+    trainable = True
+
+    def __init__(self, name, scaling, rank, lin, down_pad, up_pad):
+        self.name, self.alpha, self.rank = name, scaling, rank
+        for attr, w in (("lora_A", down_pad), ("lora_B", up_pad)):
+            if not isinstance(getattr(lin, attr, None), nn.ModuleDict):
+                setattr(lin, attr, nn.ModuleDict())
+            getattr(lin, attr)[name] = _Weight(w)
+        self._a, self._b = lin.lora_A[name], lin.lora_B[name]
+
+    down = property(lambda self: self._a.weight)
+    up = property(lambda self: self._b.weight)
+
+    def on(self, device):
+        return self                  # registered parameters move with the module
+
+    def unregister(self, lin):
+        for attr in ("lora_A", "lora_B"):
+            del getattr(lin, attr)[self.name]
+            if not len(getattr(lin, attr)):
+                delattr(lin, attr)
+
+
+def match_targets(module: nn.Module, target_modules):
+    """[(name, module)] by peft's rule (tuners_utils.check_target_module_exists with a list of targets): a module is matched when
+    its name equals a target or ends with "." + target.  In named_modules() order."""
+    targets = [t for t in (target_modules.split(",") if isinstance(target_modules, str) else list(target_modules))]
+    return [(n, m) for n, m in module.named_modules() if any(n == t or n.endswith("." + t) for t in targets)], targets
+
+
+def add_trainable(module: nn.Module, target_modules, rank, alpha=None, name="default"):
+    """`add_lora_to_model` (utils.py:450-459): a trainable adapter named `name` beside every Linear that peft's rule matches
+    (match_targets), scaling alpha / rank with alpha = rank by default.  lora_A ~ U(-1/sqrt(in), 1/sqrt(in)) — peft's
+    kaiming_uniform_(a=sqrt 5) — drawn with torch's generator in fp32 and rounded to bf16 (peft's distribution, not its draws);
+    lora_B zero.  Only bf16 Linears of DiT / ControlNet blocks take one (lora.attach's rule); a target that matches nothing is an
+    error by name.  Nothing else is frozen here: the caller decides what else trains.  Returns how many adapters were added."""
+    what = "lora.add_trainable"
+    rank = int(rank)
+    if not 1 <= rank <= MAX_RANK:
+        raise GoalForceError(f"{what}: rank {rank}: expected 1 <= r <= {MAX_RANK}")
+    scaling = _alpha(rank if alpha is None else alpha, what) / rank
+    matched, targets = match_targets(module, target_modules)
+    for t in targets:
+        if not any(n == t or n.endswith("." + t) for n, _ in matched):
+            raise GoalForceError(f"{what}: target {t!r} matches no module (peft's rule: the name equals the target or ends with '.{t}')")
+    hosted = _hosted(module)
+    for mod_name, lin in matched:
+        if not isinstance(lin, nn.Linear):
+            raise GoalForceError(f"{what}: target matches {mod_name!r}, a {type(lin).__name__}: only nn.Linear layers take an adapter")
+        _check_host(what, mod_name, lin, hosted, False, name)
+        w = lin.weight
+        if w.dtype != torch.bfloat16:
+            raise GoalForceError(f"{what}: {mod_name!r}: the weight must be bf16, got {w.dtype}")
+        if w.shape[0] % 64 or w.shape[1] % 64:       # x down^T and dy up sum over them on the GEMM (its K step)
+            raise GoalForceError(f"{what}: {mod_name!r} is {tuple(w.shape)}: a trainable adapter takes features that are multiples of 64")
+    rp = -(-rank // RANK_TILE) * RANK_TILE
+    for mod_name, lin in matched:
+        n_out, k_in = lin.weight.shape
+        dev = lin.weight.device
+        down = torch.zeros((rp, k_in), dtype=torch.bfloat16)
+        bound = 1.0 / math.sqrt(k_in)
+        down[:rank] = torch.empty((rank, k_in), dtype=torch.float32).uniform_(-bound, bound).to(torch.bfloat16)
+        ads = list(adapters(lin))
+        ads.append(TrainableAdapter(name, scaling, rank, lin, down.to(dev), torch.zeros((n_out, rp), dtype=torch.bfloat16, device=dev)))
+        lin._gf_lora = ads
+    if matched:
+        _changed()
+    return len(matched)
+
+
+def trainable(module: nn.Module):
+    """[(linear's name, the Linear, adapter)] of every trainable adapter inside `module`, in named_modules() and attach order."""
+    return [(n, m, ad) for n, m in module.named_modules() for ad in adapters(m) if ad.trainable]
+
+
+def trainable_parameters(module: nn.Module):
+    """The parameters of the trainable adapters inside `module` (lora_A then lora_B per adapter)."""
+    return [p for _, _, ad in trainable(module) for p in (ad.down, ad.up)]
+
+
+def trainable_state_dict(module: nn.Module, prefix=""):
+    """{prefix + "<linear>.lora_A.<name>.weight": [r, in], ... "lora_B.<name>.weight": [out, r]}: the true-rank tensors under peft's
+    names (the padding is cut off), detached copies on the parameters' device."""
+    out = {}
+    for n, _, ad in trainable(module):
+        dot = n + "." if n else ""
+        out[f"{prefix}{dot}lora_A.{ad.name}.weight"] = ad.down.detach()[:ad.rank].clone()
+        out[f"{prefix}{dot}lora_B.{ad.name}.weight"] = ad.up.detach()[:, :ad.rank].clone()
+    return out
+
+
+def load_trainable_state(module: nn.Module, state_dict, source=None):
+    """`mapping_lora_state_dict` + `load_state_dict(strict=False)` (utils.py:462-470, 577-583): keys spelt `lora_A.weight` /
+    `lora_B.weight` are read as the adapter "default", `lora_A.default.weight` / `lora_B.default.weight` as they are, every other
+    key is dropped; a mapped key that names no trainable adapter is reported as the reference reports it, a trainable adapter the
+    file does not name keeps its initial values, a tensor of another shape is an error (as load_state_dict makes it one).  Returns
+    (number of tensors loaded, unexpected keys)."""
+    mapped = {}
+    for key, value in state_dict.items():
+        if "lora_A.weight" in key or "lora_B.weight" in key:
+            mapped[key.replace("lora_A.weight", "lora_A.default.weight").replace("lora_B.weight", "lora_B.default.weight")] = value
+        elif "lora_A.default.weight" in key or "lora_B.default.weight" in key:
+            mapped[key] = value
+    slots = {}
+    for n, _, ad in trainable(module):
+        dot = n + "." if n else ""
+        slots[f"{dot}lora_A.{ad.name}.weight"] = (ad.down, (ad.rank, ad.down.shape[1]), (slice(0, ad.rank), slice(None)))
+        slots[f"{dot}lora_B.{ad.name}.weight"] = (ad.up, (ad.up.shape[0], ad.rank), (slice(None), slice(0, ad.rank)))
+    unexpected = [k for k in mapped if k not in slots]
+    for key, value in mapped.items():
+        if key in slots and tuple(value.shape) != slots[key][1]:
+            raise GoalForceError(f"lora.load_trainable_state: {key!r} is {tuple(value.shape)}, the adapter holds {slots[key][1]}")
+    n = 0
+    with torch.no_grad():
+        for key, value in mapped.items():
+            if key in slots:
+                p, _, at = slots[key]
+                p[at] = value.detach().to(device=p.device, dtype=p.dtype)
+                n += 1
+    if source is not None:
+        print(f"LoRA checkpoint loaded: {source}, total {len(mapped)} keys")
+    if unexpected:
+        print(f"Warning, LoRA key mismatch! Unexpected keys in LoRA checkpoint: {unexpected}")
+    if n:
+        _changed()
+    return n, unexpected

@@ -16,7 +16,7 @@ from ._lib import (EPI_BIAS, EPI_BIAS_GATE_RESID, EPI_BIAS_GELU_TANH, EPI_BIAS_M
 
 __all__ = [
     "modulation", "layernorm_modulate", "rmsnorm_rope", "gate_residual", "gemm", "flash_attn", "flash_attn_sparse", "BlockMap", "block_means", "block_means_coherence", "block_map_scores", "block_map_select", "block_map_from_qk", "patchify_im2col", "unpatchify",
-    "cfg_euler_step", "act", "add", "sub", "rel_l1", "force_map", "lora_merge", "lora_up",
+    "cfg_euler_step", "act", "add", "sub", "rel_l1", "force_map", "lora_merge", "lora_up", "lora_grad",
     "EPI_BIAS", "EPI_BIAS_GELU_TANH", "EPI_BIAS_GATE_RESID", "EPI_BIAS_RESID", "EPI_BIAS_SILU", "EPI_BIAS_MUL",
 ]
 
@@ -352,7 +352,44 @@ def lora_up(y0, t, up, scale, epilogue=EPI_BIAS, resid=None, gate=None, out=None
     return out
 
 
-VT_MIN_KV = 2048   # key sequences at least this long go through the pre-transposed-V kernel (kernel 3)
+_LORA_GRAD_WS = {}
+
+
+def _lora_grad_workspace(nbytes, device):
+    """One reusable byte buffer per (device, stream), grown to the largest shape seen — as the block maps' workspace."""
+    key = (device.index, torch.cuda.current_stream(device).cuda_stream)
+    ws = _LORA_GRAD_WS.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = _LORA_GRAD_WS[key] = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=device)
+    return ws
+
+
+def lora_grad(y, t, scale, transposed=False, out=None):
+    """out[C,R] = bf16(fp32(scale) * sum_m y[m,c] t[m,j]) (transposed: out[R,C]) — gf_lora_grad, a trainable adapter's parameter
+    gradient: dUp = lora_grad(dy, t, s), dDown = lora_grad(x, dt, s, transposed=True).  y [..., C] and t [..., R] bf16 over the same
+    rows (row strides go to the kernel), C % 8 == 0, R a multiple of 32, <= 256.  fp32 sum over the rows, one bf16 rounding; the same
+    bits on every call."""
+    _req(y, "lora_grad.y")
+    yv, M, C, ldy = _rows2d(y, "lora_grad.y")
+    R = t.shape[-1]
+    tv, ldt = _rows_like(t, "lora_grad.t", M, R)
+    if R % 32 or not 32 <= R <= LORA_MAX_RANK:
+        raise GoalForceError(f"lora_grad: padded rank {R}: expected a multiple of 32 in 32..{LORA_MAX_RANK}")
+    if C % 8:
+        raise GoalForceError(f"lora_grad.y: {C} columns: expected a multiple of 8")
+    if t.device != y.device:
+        raise GoalForceError(f"lora_grad.t: lives on {t.device}, y on {y.device}")
+    scale = _lora_scale("lora_grad", "scale", scale)
+    rows, cols = (R, C) if transposed else (C, R)
+    out = _out(out, "lora_grad.out", rows, cols, y.device)
+    lib = _lib.load()
+    ws = _lora_grad_workspace(lib.gf_lora_grad_workspace_bytes(M, C, R), y.device)
+    _lib.check(lib.gf_lora_grad(_ptr(yv), ldy, _ptr(tv), ldt, _ptr(out), out.stride(0), M, C, R, scale, int(bool(transposed)),
+                                _ptr(ws), _stream(y)), "gf_lora_grad")
+    return out
+
+
+VT_MIN_KV = 2048  # key sequences at least this long go through the pre-transposed-V kernel (kernel 3)
 # Dispatch overrides.  Every kernel ships, each for the shapes its launcher sends it; the parity tests cross-check two kernels on
 # the SAME operands, which needs a way to route a shape to the kernel that would not get it by default.  Nothing here (and nothing
 # in the library) reads an environment variable: the defaults are the shipped dispatch and only `options(...)` changes them.

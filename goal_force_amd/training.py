@@ -27,9 +27,10 @@ from typing import Optional
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import lora, ops
 from ._lib import GoalForceError
 from .dit import DiTBlock, RopeTable, WanModel, _tokens2d, q_rotation, refuse_training
+from .dit import linear as dit_linear
 
 BF = torch.bfloat16
 
@@ -241,19 +242,37 @@ def _wide_fits(x2):
 _WIDE_NAMES = ("qp", "kp", "v", "x1", "x2b")
 
 
+_LINEAR_NAMES = tuple(f"{a}.{p}" for a in ("self_attn", "cross_attn") for p in "qkvo") + ("ffn.0", "ffn.2")      # the block's ten Linears
+
+
 def _block_params(block: DiTBlock):
     named = dict(block.named_parameters())
     return [named[n] for n in _PARAM_NAMES]
 
 
+def _block_adapters(block: DiTBlock):
+    """[(layer name, adapter)] of the block's live trainable adapters: the ten Linears in _PARAM_NAMES order, attach order per layer."""
+    return [(n, ad) for n in _LINEAR_NAMES for ad in lora.live(block.get_submodule(n)) if ad.trainable]
+
+
 class DiTBlockFn(torch.autograd.Function):
-    """DiTBlock.forward (DIT:197-230) with a hand-written backward; inputs x2 [S,D], ctx2 [L,D], t_mod [1,6,D]."""
+    """DiTBlock.forward (DIT:197-230) with a hand-written backward; inputs x2 [S,D], ctx2 [L,D], t_mod [1,6,D].  After the 27
+    block parameters come lora_A, lora_B of every live trainable adapter (_block_adapters' order): peft's unmerged forward
+    y + s * (x A^T) B^T is differentiated beside the layer —
+        t = bf16(x A^T), dt = bf16(dy B);  dB = s dy^T t,  dA = s dt^T x  (ops.lora_grad: one pass over dy / x each);
+        dx = dx_base + s dt A  (ops.lora_up on the base layer's dx, in place)
+    with s applied in these three consumers and never to dy (no extra pass over [M, N])."""
 
     @staticmethod
     def forward(ctx, block, rope, x2, ctx2, t_mod, *params):
         ctx.block, ctx.rope = block, rope
         refuse_training(block)
-        ctx.param_needs = [p.requires_grad for p in params]
+        ctx.adapters = _block_adapters(block)
+        if len(params) != len(_PARAM_NAMES) + 2 * len(ctx.adapters):
+            raise GoalForceError(f"DiTBlockFn: {len(params)} parameters for a block with {len(ctx.adapters)} live trainable adapters: "
+                                 "expected the 27 block parameters, then lora_A, lora_B per adapter (training.block_forward)")
+        ctx.param_needs = [p.requires_grad for p in params[:len(_PARAM_NAMES)]]
+        ctx.lora_needs = [p.requires_grad for p in params[len(_PARAM_NAMES):]]
         ctx.q_prescale = bool(ops.option("attn_q_prescale"))       # what the forward's self-attention saw is what the backward rebuilds (dit.q_rotation)
         keep = ({"wide": True} if _wide_fits(x2) else {}) if KEEP_ATTENTION else None
         with torch.no_grad():
@@ -280,26 +299,45 @@ class DiTBlockFn(torch.autograd.Function):
         kept = ctx.saved_tensors[3:5]
         wide = dict(zip(_WIDE_NAMES, ctx.saved_tensors[5:])) if ctx.wide else None
         need = dict(zip(_PARAM_NAMES, ctx.param_needs))
-        any_param = any(ctx.param_needs)
+        any_param = any(ctx.param_needs) or any(ctx.lora_needs)
         eps, dev, d = block.eps, x.device, block.dim
         sa, ca, heads, hd = block.self_attn, block.cross_attn, block.num_heads, block.dim // block.num_heads
         dout = dout.contiguous()
         g = {}                                              # parameter gradients by name
 
-        def lin(xin, layer):
-            return ops.gemm(xin, layer.weight, layer.bias)
+        lg = [None] * len(ctx.lora_needs)                   # adapter gradients: lora_A, lora_B per adapter
+        by_layer = {}
+        for i, (name, ad) in enumerate(ctx.adapters):
+            by_layer.setdefault(name, []).append((i, ad))
+
+        def lin(xin, layer, **kw):
+            return dit_linear(xin, layer, **kw)             # the layer as the forward ran it: its live adapters included
 
         def lin_bwd(dy, xin, layer, prefix, want_dx=True):
             if need[prefix + ".weight"]:
                 g[prefix + ".weight"] = linear_dw(dy, xin)
             if need[prefix + ".bias"]:
                 g[prefix + ".bias"] = bias_grad(dy)
-            return linear_dx(dy, layer.weight) if want_dx else None
+            dx = linear_dx(dy, layer.weight) if want_dx else None
+            for i, ad in by_layer.get(prefix, ()):
+                need_a, need_b = ctx.lora_needs[2 * i], ctx.lora_needs[2 * i + 1]
+                if not (want_dx or need_a or need_b):
+                    continue
+                down, up = ad.down.detach(), ad.up.detach()
+                if need_b:
+                    lg[2 * i + 1] = ops.lora_grad(dy, ops.gemm(xin, down), ad.alpha)
+                if want_dx or need_a:
+                    dt = ops.gemm(dy, ops.transpose_pad(up, up.shape[0]))          # dy B on a small transposed copy [rank_pad, n_out]
+                    if need_a:
+                        lg[2 * i] = ops.lora_grad(xin, dt, ad.alpha, transposed=True)
+                    if want_dx:
+                        ops.lora_up(dx, dt, ops.transpose_pad(down, down.shape[0]), ad.alpha, out=dx)
+            return dx
 
         # ---- recompute the forward, un-fused, keeping the intermediates (DIT:218-229); what the forward kept (`wide`) is taken as it
         # is, and what would only feed a parameter gradient nobody asked for (a frozen block) is not computed
         mod = ops.modulation(block.modulation, t_mod.contiguous(), onep_mask=0b010010)
-        need_h1 = wide is None or any(need[f"self_attn.{n}.weight"] for n in "qkv")
+        need_h1 = wide is None or any(need[f"self_attn.{n}.weight"] or f"self_attn.{n}" in by_layer for n in "qkv")
         h1 = ops.layernorm_modulate(x, scale1p=mod[1], shift=mod[0], eps=eps) if need_h1 else None
         if wide is not None:
             qp, kp, vv = wide["qp"], wide["kp"], wide["v"]
@@ -318,11 +356,11 @@ class DiTBlockFn(torch.autograd.Function):
         ops.rmsnorm_rope(q2n, ca.norm_q.weight, None, None, hd, ca.norm_q.eps)
         ops.rmsnorm_rope(k2n, ca.norm_k.weight, None, None, hd, ca.norm_k.eps)
         a2, lse2 = ops.flash_attn_lse(q2n, k2n, v2, heads)
-        x2b = wide["x2b"] if wide is not None else ops.gemm(a2, ca.o.weight, ca.o.bias, epilogue=ops.EPI_BIAS_RESID, resid=x1)
+        x2b = wide["x2b"] if wide is not None else lin(a2, ca.o, epilogue=ops.EPI_BIAS_RESID, resid=x1)
         h3 = ops.layernorm_modulate(x2b, scale1p=mod[4], shift=mod[3], eps=eps)
         u = lin(h3, block.ffn[0])
         need_y = need["modulation"]                                                      # y: only the gate's gradient reads it
-        f = ops.act(u, "gelu_tanh") if (need_y or need["ffn.2.weight"]) else None
+        f = ops.act(u, "gelu_tanh") if (need_y or need["ffn.2.weight"] or "ffn.2" in by_layer) else None
         y = lin(f, block.ffn[2]) if need_y else None
 
         def acc():
@@ -382,30 +420,35 @@ class DiTBlockFn(torch.autograd.Function):
             rows = torch.stack([dshift1, dscale1, dgate1, dshift2, dscale2, dgate2]).contiguous()
             g["modulation"] = ops.f32_to_bf16(rows).view(block.modulation.shape)
         grads = [g.get(n) if nd else None for n, nd in zip(_PARAM_NAMES, ctx.param_needs)]
-        return (None, None, dx, None, None, *grads)
+        return (None, None, dx, None, None, *grads, *lg)
 
 
 def block_forward(block: DiTBlock, x2, ctx2, t_mod, rope: RopeTable):
-    return DiTBlockFn.apply(block, rope, x2, ctx2, t_mod, *_block_params(block))
+    return DiTBlockFn.apply(block, rope, x2, ctx2, t_mod, *_block_params(block), *(p for _, ad in _block_adapters(block) for p in (ad.down, ad.up)))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
 # model_fn with a tape, loss, optimiser
 def model_fn_train(dit: WanModel, controlnet, latents, timestep, context, y, control_signal_video_latents):
-    """model_fn_wan_video (GF:1349-1591) with gradients to the ControlNet parameters.  The DiT expert is frozen: its
-    embeddings run without a tape, its blocks back-propagate activations only."""
+    """model_fn_wan_video (GF:1349-1591) with gradients to the ControlNet parameters and to the trainable LoRA adapters of either
+    model's blocks (lora.add_trainable).  The DiT expert's own weights are frozen: its embeddings run without a tape, its blocks
+    back-propagate activations (and adapter gradients) only.  controlnet=None: the plain expert, no injection
+    (`--lora_base_model dit` without `--trainable_models`)."""
     with torch.no_grad():
         t, t_mod = dit.time_embed(timestep)
         ctx2 = dit.embed_text(context)[0]
         x, (f, h, w) = dit.patchify(latents, extra=y if (y is not None and dit.require_vae_embedding) else None)
         rope = dit.rope_table(f, h, w, latents.device)
-        pe = controlnet.controlnet_patch_embedding
-        kpad = _pad64(pe.patch_embedding.weight.shape[1] * 4)
-        cols = ops.patchify_im2col(control_signal_video_latents[0].contiguous(), None, kpad=kpad)
+        if controlnet is not None:
+            pe = controlnet.controlnet_patch_embedding
+            kpad = _pad64(pe.patch_embedding.weight.shape[1] * 4)
+            cols = ops.patchify_im2col(control_signal_video_latents[0].contiguous(), None, kpad=kpad)
         hmod = ops.modulation(dit.head.modulation, t.contiguous(), onep_mask=0b10)
     x = x[0]
-    c = PatchEmbedFn.apply(cols, pe.patch_embedding.weight, pe.patch_embedding.bias)
-    n_cn = controlnet.controlnet_dit.num_layers
+    n_cn = 0
+    if controlnet is not None:
+        c = PatchEmbedFn.apply(cols, pe.patch_embedding.weight, pe.patch_embedding.bias)
+        n_cn = controlnet.controlnet_dit.num_layers
     for i, block in enumerate(dit.blocks):
         if i < n_cn:
             c = block_forward(controlnet.controlnet_dit.blocks[i], c, ctx2, t_mod, rope)
@@ -434,7 +477,7 @@ def training_loss(pipe, *, input_latents, noise, context, y, control_signal_vide
     timestep = sch.timesteps[timestep_id:timestep_id + 1].to(dtype=pipe.torch_dtype, device=pipe.device)
     latents = sch.add_noise(input_latents, noise, timestep)
     target = sch.training_target(input_latents, noise, timestep)
-    pred = model_fn_train(dit or pipe.dit, controlnet or pipe.controlnet, latents, timestep, context, y,
+    pred = model_fn_train(dit or pipe.dit, controlnet or getattr(pipe, "controlnet", None), latents, timestep, context, y,
                           control_signal_video_latents)
     return MseLossFn.apply(pred[0], target[0].contiguous(), float(sch.training_weight(timestep)))
 
@@ -567,11 +610,43 @@ class ConstantLR:
             self.optimizer.lr = self.optimizer.lr * (1.0 / self.factor)
 
 
+def _pipe_models(pipe):
+    """[(name, module)] of the pipeline's models that can hold trainable parameters here: the ControlNet and the experts."""
+    out = []
+    for name in ("controlnet", "dit", "dit2"):
+        m = getattr(pipe, name, None)
+        if isinstance(m, nn.Module):
+            out.append((name, m))
+    return out
+
+
+def trainable_named_parameters(pipe, padded=False):
+    """{"pipe.<model>.<name>": tensor} of what launch_training_task optimises, in a fixed order: the ControlNet's parameters that
+    require grad under their own names, then every trainable LoRA adapter of the pipeline's models under peft's names
+    (`...lora_A.<adapter>.weight` / `...lora_B.<adapter>.weight`) — the true-rank tensors (what a checkpoint holds), or with
+    padded=True the parameters themselves (what the optimiser steps)."""
+    out = {}
+    for model_name, m in _pipe_models(pipe):
+        lora_ids = {id(p) for p in lora.trainable_parameters(m)}
+        if model_name == "controlnet":
+            out.update({f"pipe.{model_name}.{k}": v for k, v in m.named_parameters() if v.requires_grad and id(v) not in lora_ids})
+        if padded:
+            for n, _, ad in lora.trainable(m):
+                for attr, p in (("lora_A", ad.down), ("lora_B", ad.up)):
+                    if p.requires_grad:
+                        out[f"pipe.{model_name}.{n}.{attr}.{ad.name}.weight"] = p
+        else:
+            out.update(lora.trainable_state_dict(m, f"pipe.{model_name}."))
+    return out
+
+
 class ModelLogger:
     """utils.py:592-650: counts optimiser steps, writes `step-<N>.safetensors` every `save_steps` (and once more at the end if the last
     step was not a multiple), or `epoch-<k>.safetensors` when save_steps is None.  Checkpoint keys: the trainable parameters under
     their names in the training module, `pipe.controlnet.<name>` (the scripts pass --remove_prefix_in_ckpt "pipe.dit.", which leaves
-    them as they are; `load_controlnet_weights` strips `pipe.controlnet.`, GF:176-178).  Written by rank 0 only."""
+    them as they are; `load_controlnet_weights` strips `pipe.controlnet.`, GF:176-178), and the trainable LoRA adapters as
+    `pipe.<model>.<peft name>` in their true rank — with `--remove_prefix_in_ckpt pipe.dit.` the file pipe.load_lora and
+    lora.attach read.  Written by rank 0 only."""
 
     def __init__(self, output_path, remove_prefix_in_ckpt=None, log=None, log_every=10):
         self.output_path, self.remove_prefix_in_ckpt, self.num_steps = output_path, remove_prefix_in_ckpt, 0
@@ -601,7 +676,7 @@ class ModelLogger:
             if dist.get_rank() != 0:
                 return None
         from safetensors.torch import save_file
-        sd = {"pipe.controlnet." + k: v.detach().cpu().contiguous() for k, v in pipe.controlnet.named_parameters() if v.requires_grad}
+        sd = {k: v.detach().cpu().contiguous() for k, v in trainable_named_parameters(pipe).items()}
         if self.remove_prefix_in_ckpt is not None:
             sd = {(k[len(self.remove_prefix_in_ckpt):] if k.startswith(self.remove_prefix_in_ckpt) else k): v for k, v in sd.items()}
         os.makedirs(self.output_path, exist_ok=True)
@@ -662,7 +737,11 @@ def launch_training_task(dataset, model, learning_rate: float = 1e-5, weight_dec
         def forward(pipe_, data):
             return training_loss(pipe_, **forward_preprocess(pipe_, data, extra_inputs=extra), max_timestep_boundary=tmax,
                                  min_timestep_boundary=tmin)
-    params = [p_ for p_ in pipe.controlnet.parameters() if p_.requires_grad]
+    params = list(trainable_named_parameters(pipe, padded=True).values())
+    if not params:
+        raise GoalForceError("launch_training_task: nothing to train: no ControlNet parameter requires grad and no model carries a "
+                             "trainable LoRA adapter (lora.add_trainable)")
+    has_lora = any(lora.trainable(m) for _, m in _pipe_models(pipe))
     optimizer = AdamW(params, lr=learning_rate, weight_decay=weight_decay)
     scheduler = ConstantLR(optimizer)
     print("Dataset size: ", len(dataset))
@@ -709,6 +788,9 @@ def launch_training_task(dataset, model, learning_rate: float = 1e-5, weight_dec
             allreduce_gradients(params)
             grad_norm = optimizer.grad_norm() if max_grad_norm > -1 else None                   # clip_grad_norm_ returns the norm BEFORE clipping
             optimizer.step(max_grad_norm=max_grad_norm if max_grad_norm > -1 else None, grad_norm=grad_norm)
+            if has_lora:
+                from .dit import invalidate_caches
+                invalidate_caches()              # no copy derived from adapter values (memoised context projections) outlives the step
             logger.on_step_end(pipe, loss.detach(), optimizer.lr, grad_norm=grad_norm, save_steps=save_steps)
             # Accelerate's prepared scheduler advances the wrapped one `num_processes` times per training step (accelerate/scheduler.py,
             # AcceleratedScheduler.step without split_batches): on the reference's 4-process runs the lr / 3 phase lasts 2 steps, not 5
@@ -722,9 +804,10 @@ def launch_training_task(dataset, model, learning_rate: float = 1e-5, weight_dec
 
 def wan_parser():
     """`wan_parser` (utils.py:854-900): the training script's command line, argument for argument and default for default (pinned
-    against the reference's own parser object by tests/golden/g18).  Arguments of branches Goal Force never trains (LoRA, strided
-    ControlNet, gradient-checkpoint offload, wandb) are accepted so that the reference's shell scripts run unchanged;
-    scripts/train.py refuses the ones that would change what is computed."""
+    against the reference's own parser object by tests/golden/g18).  The four --lora_* arguments do what switch_pipe_to_training_mode
+    does with them (scripts/train.py::add_lora).  Arguments of branches Goal Force never trains (strided ControlNet,
+    gradient-checkpoint offload, wandb) are accepted so that the reference's shell scripts run unchanged; scripts/train.py refuses
+    the ones that would change what is computed."""
     import argparse
     ap = argparse.ArgumentParser(description="Simple example of a training script.")
     ap.add_argument("--dataset_base_path", type=str, nargs="+", default="", required=True, help="Base path(s) of the dataset.")

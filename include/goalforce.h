@@ -591,6 +591,27 @@ GF_API int gf_lora_up(const void* y0, int64_t ldy, const void* t, int64_t ldt, c
                       int64_t M, int64_t N, int64_t rank_pad, float scale, int epilogue, const void* resid, int64_t ldr,
                       const void* gate, void* stream);
 
+/* gf_lora_grad (gf_lora_grad.hip) — a trainable adapter's parameter gradients, the sum over the tokens:
+ *     out[c, j] = bf16( fp32(scale) * sum_{m < M} Y[m, c] * T[m, j] )        c < C, j < rank_pad;  transposed = 1: stored at out[j, c]
+ * dUp [n_out, r] = gf_lora_grad(dy, t = bf16(x down^T), scale); dDown [r, k_in] = gf_lora_grad(x, dt = bf16(dy up), scale, transposed).
+ * Y [M, ldy] and T [M, ldt] bf16, read row-major as they are (no transposed copy is written); out bf16 [C, ldo] or, transposed,
+ * [rank_pad, ldo].  fp32 accumulation on v_mfma_f32_16x16x32_bf16, nothing rounded before the last token, scale applied to the fp32
+ * sum, ONE bf16 rounding per element: at scale 1 (the reference's lora_alpha = r) torch's bf16 autograd chain, at any other scale
+ * one rounding tighter than it.  A zero sum is stored as +0 for every scale, so columns of T that are zero (the rank's padding) give
+ * +0, and M = 0 writes +0 everywhere.
+ * The tokens are split into gf_lora_grad_slabs(M, C, rank_pad) slabs — slab s is rows s * gf_lora_grad_slab_rows(...) up to the
+ * next slab's first row or M — each summed in ascending tiles of 64 tokens into an fp32 partial in `workspace`
+ * (gf_lora_grad_workspace_bytes bytes, 16-byte aligned, caller-owned, one per stream in flight; may be null when that is 0); a
+ * second kernel adds the partials in ascending slab order.  No atomics: two calls on the same operands give the same bits.  All
+ * three are pure functions of (M, C, rank_pad) and return 0 for a shape gf_lora_grad refuses (and for M = 0).
+ * M >= 0; C % 8 == 0; rank_pad a multiple of 32, <= 256; every leading dimension a multiple of 8 that covers its row; 16-byte
+ * aligned bases; scale finite.  Every refusal leaves out untouched. */
+GF_API int64_t gf_lora_grad_slabs(int64_t M, int64_t C, int64_t rank_pad);
+GF_API int64_t gf_lora_grad_slab_rows(int64_t M, int64_t C, int64_t rank_pad);
+GF_API int64_t gf_lora_grad_workspace_bytes(int64_t M, int64_t C, int64_t rank_pad);
+GF_API int gf_lora_grad(const void* Y, int64_t ldy, const void* T, int64_t ldt, void* out, int64_t ldo, int64_t M, int64_t C,
+                        int64_t rank_pad, float scale, int transposed, void* workspace, void* stream);
+
 /* ---- Canny-edge control signal (ControlSignalDataset_CannyEdge._generate_control_video, src/goal_force/unified_dataset.py:559-578;
  * the reference calls cv2 / controlnet_aux per frame on the host — absent here: OpenCV's published algorithm restated, "parity unpinned").
  * All images are uint8 [frames, H, W, 3] (HWC), all tables device arrays built by goal_force_amd/canny.py.

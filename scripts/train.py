@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""ControlNet training launcher on the MI355X training step — mirror of the reference's scripts/train/train.py: the SAME command
+"""ControlNet / LoRA training launcher on the MI355X training step — mirror of the reference's scripts/train/train.py: the SAME command
 line (`wan_parser`, src/goal_force/utils.py:854-900), dataset mux (train.py:126-197), training module (train.py:12-124: load the
-models, freeze all but `--trainable_models controlnet`, scheduler in training mode, optional `--controlnet_checkpoint`) and loop
+models, freeze all but `--trainable_models controlnet`, scheduler in training mode, trainable LoRA adapters on `--lora_base_model`
+(`--lora_target_modules`, `--lora_rank`, `--lora_checkpoint`; utils.py:569-584), optional `--controlnet_checkpoint`) and loop
 (`launch_training_task`, utils.py:734-826).  One process per GPU: where the reference starts `accelerate launch` with a DeepSpeed
 ZeRO-2 config, start this with `python -m torch.distributed.run --nproc-per-node N scripts/train.py ...` (gradients are averaged over
 RCCL, goal_force_amd/training.py::allreduce_gradients; 288 GB of HBM hold the frozen expert, the ControlNet, its fp32 moments and the
@@ -39,6 +40,46 @@ def model_configs(args):
     return cfgs
 
 
+def check_args(args):
+    """What the HIP training step differentiates: the ControlNet (`--trainable_models controlnet`), LoRA adapters on one model's
+    blocks (`--lora_base_model dit`; `--trainable_models` may then be empty), or both.  Needs no device."""
+    if args.apply_strided_controlnet or args.controlnet_stride is not None:
+        raise NotImplementedError("strided ControlNet is not used by Goal Force")
+    if args.control_signal_type not in ("canny_edge", "direct_force_and_goal_force_and_mass"):
+        raise NotImplementedError(args.control_signal_type)                                            # train.py:33-38
+    if getattr(args, "enable_fp8_training", False):
+        raise NotImplementedError("--enable_fp8_training: trainable LoRA adapters run on bf16 layers only (the backward recomputes the block in bf16)")
+    trainable = args.trainable_models or ""
+    if args.lora_base_model is None:
+        if args.lora_checkpoint is not None:
+            raise NotImplementedError("--lora_checkpoint needs --lora_base_model (the reference ignores it without one; here it is an error)")
+        if trainable != "controlnet":
+            raise NotImplementedError("--trainable_models controlnet is what the HIP training step differentiates")
+    else:
+        if args.lora_base_model not in ("dit", "dit2", "controlnet"):
+            raise NotImplementedError(f"--lora_base_model {args.lora_base_model}: adapters train on the blocks of dit, dit2 or controlnet")
+        if trainable not in ("", "controlnet"):
+            raise NotImplementedError("--trainable_models: empty or controlnet beside --lora_base_model")
+        if not 1 <= args.lora_rank <= 256:
+            raise NotImplementedError(f"--lora_rank {args.lora_rank}: expected 1 <= r <= 256")
+
+
+def add_lora(pipe, args):
+    """switch_pipe_to_training_mode's LoRA part (utils.py:569-584): inject trainable adapters into `--lora_base_model` (after the
+    freeze, so only they and `--trainable_models` train), then optionally restore them from `--lora_checkpoint`."""
+    if args.lora_base_model is None:
+        return 0
+    from goal_force_amd import lora
+    from goal_force_amd.checkpoints import load_state_dict
+    model = getattr(pipe, args.lora_base_model, None)
+    if model is None:
+        raise NotImplementedError(f"--lora_base_model {args.lora_base_model}: the pipeline holds no such model")
+    n = lora.add_trainable(model, args.lora_target_modules.split(","), args.lora_rank)
+    if args.lora_checkpoint is not None:
+        lora.load_trainable_state(model, load_state_dict(args.lora_checkpoint), source=args.lora_checkpoint)
+    return n
+
+
 class WanTrainingModule:
     """train.py:12-124 around the HIP pipeline: what launch_training_task needs of it (`.pipe`, `.extra_inputs`, the timestep
     boundaries)."""
@@ -46,15 +87,7 @@ class WanTrainingModule:
     def __init__(self, args, device):
         import torch
         from goal_force_amd.pipeline import ModelConfig, WanVideoPipeline
-        for name in ("lora_base_model", "lora_checkpoint"):
-            if getattr(args, name) is not None:
-                raise NotImplementedError(f"--{name}: LoRA training is outside the Goal-Force path (the scripts train the ControlNet)")
-        if args.apply_strided_controlnet or args.controlnet_stride is not None:
-            raise NotImplementedError("strided ControlNet is not used by Goal Force")
-        if args.control_signal_type not in ("canny_edge", "direct_force_and_goal_force_and_mass"):
-            raise NotImplementedError(args.control_signal_type)                                            # train.py:33-38
-        if (args.trainable_models or "") != "controlnet":
-            raise NotImplementedError("--trainable_models controlnet is what the HIP training step differentiates")
+        check_args(args)
         self.pipe = WanVideoPipeline.from_pretrained(
             torch_dtype=torch.bfloat16, device=device, model_configs=model_configs(args), controlnet=True,
             controlnet_num_layers=args.controlnet_num_layers,
@@ -62,7 +95,8 @@ class WanTrainingModule:
                                          path=f"{MODELS}/Wan2.1-T2V-1.3B/google/umt5-xxl"))               # train.py:43-55
         self.pipe.scheduler.set_timesteps(1000, training=True)                                             # utils.py:560
         self.pipe.freeze_except([] if args.trainable_models is None else args.trainable_models.split(","))   # utils.py:563
-        if args.controlnet_checkpoint is not None:                                                         # utils.py:586-590
+        add_lora(self.pipe, args)                                                                          # utils.py:569-584
+        if args.controlnet_checkpoint is not None:                                                        # utils.py:586-590
             self.pipe.load_controlnet_weights(self.pipe.controlnet, args.controlnet_checkpoint, torch_dtype=torch.bfloat16)
             print(f"ControlNet checkpoint loaded: {args.controlnet_checkpoint}, total {len(self.pipe.controlnet.state_dict())} keys")
         else:
