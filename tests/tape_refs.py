@@ -361,6 +361,63 @@ def _sub_sd(sd, pre):
     return {k[len(pre):]: v for k, v in sd.items() if k.startswith(pre)}
 
 
+FWD_FAULTS = ("inject_prev_state", "inject_before_block", "last_cn_not_injected", "cat_y_latents", "head_shift_scale_swapped")
+
+
+def model_fwd(cfg, dit_sd, cn_sd, n_cn, latents, y, control, context, timestep, order=0, block=None, fault=None):
+    """The forward of model_fn (GF:1349-1591) on the pieces above, shared by model_chain (the training tape) and tests/inference_refs.py
+    (the inference forward): time / text embedding, the patch GEMM on cat([latents, y]), the ControlNet patch embedding, ControlNet
+    block i before DiT block i, the injection GEMM with its residual epilogue, the head, unpatchify.  `block(sd, x, ctx, t_mod, grid,
+    stack, i)` -> an object with `.out` (default: block_fwd; stack "cn" | "dit").  -> a namespace: `taps[i]` the residual stream after
+    DiT block i BEFORE the injection, `x` the stream the head reads, `tok` the head's output [S, 4 out_dim], `pred` [out_dim, f, 2h, 2w].
+    `fault`: one of FWD_FAULTS (a wrong line of the forward)."""
+    assert fault is None or fault in FWD_FAULTS, fault
+    if block is None:
+        block = lambda sd, x, ctx, t_mod, grid, stack, i: block_fwd(cfg, sd, x, ctx, t_mod, grid, order)          # noqa: E731
+    d, eps = cfg["dim"], cfg["eps"]
+    m = types.SimpleNamespace()
+    m.t, m.t_mod = wo.time_embed(timestep, dit_sd, cfg["freq_dim"], d)               # bf16 linears: fp32 sums rounded once
+    m.ctx = wo.text_embed(context, dit_sd)[0]
+    parts = [latents] if y is None else ([y, latents] if fault == "cat_y_latents" else [latents, y])
+    m.cols = im2col(torch.cat(parts, dim=1)[0])
+    x = _gemm(m.cols, dit_sd["patch_embedding.weight"].reshape(d, -1), dit_sd["patch_embedding.bias"], order)
+    f_, h_, w_ = latents.shape[2], latents.shape[3] // 2, latents.shape[4] // 2
+    m.grid = grid = (f_, h_, w_)
+    c = None
+    if n_cn:
+        pe = "controlnet_patch_embedding.patch_embedding."
+        m.ccols = im2col(control[0])
+        c = _gemm(m.ccols, cn_sd[pe + "weight"].reshape(d, -1), cn_sd[pe + "bias"], order)
+    m.cn_fwd, m.dit_fwd, m.states, m.taps = [], [], [], []
+
+    def inject(i, x):
+        j = max(i - 1, 0) if fault == "inject_prev_state" else i
+        zw = cn_sd[f"controlnet_zero_convs_after.{i}.weight"]
+        return _gemm(m.states[j], zw.reshape(d, d), cn_sd[f"controlnet_zero_convs_after.{i}.bias"], order, GR.EPI_RESID, x)
+
+    injected = n_cn - 1 if fault == "last_cn_not_injected" else n_cn
+    for i in range(cfg["num_layers"]):
+        if i < n_cn:
+            m.cn_fwd.append(block(_sub_sd(cn_sd, f"controlnet_dit.blocks.{i}."), c, m.ctx, m.t_mod, grid, "cn", i))
+            c = m.cn_fwd[-1].out
+            m.states.append(c)
+            if fault == "inject_before_block" and i < injected:
+                x = inject(i, x)
+        m.dit_fwd.append(block(_sub_sd(dit_sd, f"blocks.{i}."), x, m.ctx, m.t_mod, grid, "dit", i))
+        x = m.dit_fwd[-1].out
+        m.taps.append(x)
+        if i < injected and fault != "inject_before_block":
+            x = inject(i, x)
+    m.x = x
+    m.hmod = FR.modulation_ref(dit_sd["head.modulation"][0], m.t, 0b10)
+    shift, scale1p = (m.hmod[1], m.hmod[0]) if fault == "head_shift_scale_swapped" else (m.hmod[0], m.hmod[1])
+    hx = FR.layernorm_f32(x, scale1p=scale1p, shift=shift, eps=eps)
+    m.tok = _gemm(hx, dit_sd["head.head.weight"], dit_sd["head.head.bias"], order)
+    co = cfg["out_dim"]
+    m.pred = m.tok.reshape(f_, h_, w_, 2, 2, co).permute(5, 0, 1, 3, 2, 4).reshape(co, f_, 2 * h_, 2 * w_)
+    return m
+
+
 def model_chain(cfg, dit_sd, cn_sd, n_cn, inputs, timestep_id, order=0, fault=None):
     """(loss, {ControlNet parameter: gradient bf16}) of training_loss + backward (model_fn_train, GF:1349-1591 with the tape)."""
     assert fault is None or fault in MODEL_FAULTS, fault
@@ -372,31 +429,10 @@ def model_chain(cfg, dit_sd, cn_sd, n_cn, inputs, timestep_id, order=0, fault=No
     x0, noise = inputs["input_latents"], inputs["noise"]
     latents = (1 - sigma) * x0 + sigma * noise                                     # bf16 eager arithmetic, as the scheduler's
     target = noise - x0
-    t, t_mod = wo.time_embed(timestep, dit_sd, cfg["freq_dim"], d)                   # bf16 linears: fp32 sums rounded once
-    ctx = wo.text_embed(inputs["context"], dit_sd)[0]
-    cols = im2col(torch.cat([latents, inputs["y"]], dim=1)[0])
-    x = _gemm(cols, dit_sd["patch_embedding.weight"].reshape(d, -1), dit_sd["patch_embedding.bias"], order)
-    f_, h_, w_ = latents.shape[2], latents.shape[3] // 2, latents.shape[4] // 2
-    grid = (f_, h_, w_)
+    m = model_fwd(cfg, dit_sd, cn_sd, n_cn, latents, inputs["y"], inputs["control"], inputs["context"], timestep, order)
+    f_, h_, w_ = m.grid
+    x, hmod, states, cn_fwd, dit_fwd, ccols, pred, co = m.x, m.hmod, m.states, m.cn_fwd, m.dit_fwd, m.ccols, m.pred, cfg["out_dim"]
     pe = "controlnet_patch_embedding.patch_embedding."
-    ccols = im2col(inputs["control"][0])
-    c = _gemm(ccols, cn_sd[pe + "weight"].reshape(d, -1), cn_sd[pe + "bias"], order)
-    cn_fwd, dit_fwd, states = [], [], []
-    for i in range(cfg["num_layers"]):
-        if i < n_cn:
-            cn_fwd.append(block_fwd(cfg, _sub_sd(cn_sd, f"controlnet_dit.blocks.{i}."), c, ctx, t_mod, grid, order))
-            c = cn_fwd[-1].out
-            states.append(c)
-        dit_fwd.append(block_fwd(cfg, _sub_sd(dit_sd, f"blocks.{i}."), x, ctx, t_mod, grid, order))
-        x = dit_fwd[-1].out
-        if i < n_cn:
-            zw = cn_sd[f"controlnet_zero_convs_after.{i}.weight"]
-            x = _gemm(states[i], zw.reshape(d, d), cn_sd[f"controlnet_zero_convs_after.{i}.bias"], order, GR.EPI_RESID, x)
-    hmod = FR.modulation_ref(dit_sd["head.modulation"][0], t, 0b10)
-    hx = FR.layernorm_f32(x, scale1p=hmod[1], shift=hmod[0], eps=eps)
-    tok = _gemm(hx, dit_sd["head.head.weight"], dit_sd["head.head.bias"], order)
-    co = cfg["out_dim"]
-    pred = tok.reshape(f_, h_, w_, 2, 2, co).permute(5, 0, 1, 3, 2, 4).reshape(co, f_, 2 * h_, 2 * w_)
     loss, dpred = loss_chain(pred.contiguous(), target[0].contiguous(), float(weights[tid]))
     # ---- backward
     grads = {}
@@ -452,11 +488,13 @@ def _as2d(name, t):
     return t.reshape(1, -1), ("all",)
 
 
-def row_stat(name, got, chain0, ref):
+def row_stat(name, got, chain0, ref, axes=None):
     """dict(worst, where, zero_bad, noise): the worst ratio over the tensor's slices and which slice; the number of slices whose
-    reference is identically zero but `got` is not; the chain's median dev_rms over the rows (fault `row_eps` is built from it)."""
+    reference is identically zero but `got` is not; the chain's median dev_rms over the rows (fault `row_eps` is built from it).
+    `axes` (tests/inference_refs.py): the slices of a 2-D tensor, ("row",), ("col",) or both, instead of what the name says."""
     assert got.shape == ref.shape == chain0.shape, (name, got.shape, chain0.shape, ref.shape)
-    g, axes = _as2d(name, got)
+    g, named_axes = _as2d(name, got)
+    axes = named_axes if axes is None else axes
     c, r = _as2d(name, chain0)[0], _as2d(name, ref)[0]
     worst, where, zero_bad, noise = 0.0, None, 0, 0.0
     for ax in axes:

@@ -11,12 +11,15 @@ of tests/gemm_refs.py, `--only vaepin` (opt-in) the VAE's convolution kernels ag
 through the same bars, `--only crossfold` (opt-in) the folded cross-attention's two kernels through the raw C ABI against the bars of
 tests/cross_fold_refs.py, `--only sagepin` (opt-in) the SageAttention kernels on the exact classes and through the two bars of
 tests/sage_refs.py, `--only tape` (opt-in) the training tape of one block (training.DiTBlockFn.backward) at random token grids, context
-lengths, keep levels and parameter subsets through the row statistic of tests/tape_refs.py."""
+lengths, keep levels and parameter subsets through the row statistic of tests/tape_refs.py, `--only infwd` (opt-in) the inference forward
+of one block (DiTBlock.forward) at random token grids, prompt lengths, head counts and cross-attention options, each on the route the
+dispatch gives it, through the row statistic of tests/inference_refs.py."""
 import argparse
 import math
 import os
 import random
 import sys
+import types
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -742,10 +745,55 @@ def case_tape(rnd, g):
             f"{where[1]['worst']:.3f}"), err, 1.0
 
 
-CASES = {"tape": case_tape, "gemmpin": case_gemmpin, "vaepin": case_vaepin, "gemm": case_gemm, "attn": case_attn, "rows": case_rows, "cfg": case_cfg, "attnbwd": case_attnbwd, "fp8": case_fp8,
+def case_infwd(rnd, g):
+    """DiTBlock.forward held as tests/test_inference_forward_gpu.py holds it (helper: tests/inference_refs.py): a block at 2 or 4 heads on a
+    random token grid, a 512-row context with a random prompt length p (or no run), q pre-scale and the two cross-attention options,
+    against fp64 through the row statistic, each result against the restatement of the route inference_refs.route_of names; err = the
+    worst ratio over its group's FWD_ROW_BAR (inf where the calls seen are not that route's, or a zero slice is not zero); bar 1."""
+    for p in (os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests", "golden")):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    import inference_refs as R
+    from goal_force_amd.dit import DiTBlock, RopeTable, precompute_freqs_cis_3d
+    # at least 72 tokens, the fewest FWD_ROW_WORST was measured at: a channel column over a handful of token rows is a handful of random
+    # variables (at 6 tokens the CPU restatement itself reaches 2.1 against the column bar of 1.70), outside what the bars were measured for
+    grid = (1, 1, 1)
+    while grid[0] * grid[1] * grid[2] < 72:
+        grid = (rnd.randrange(1, 4), rnd.randrange(2, 9), rnd.randrange(3, 14))
+    p = rnd.choice([None, 0, 511, 510, 63, 62, rnd.randrange(0, 64), rnd.randrange(0, 512)])
+    opts = {k: False for k in ("fold_cross_o", "fold_pad_keys") if rnd.random() < 0.2}
+    case = R._bcase(rnd.choice(["TINY", "H4"]), grid, R.CTX_LEN if p is not None else rnd.choice([7, R.CTX_LEN]), p, rnd.random() < 0.7,
+                    seed=rnd.randrange(1 << 20), **opts)
+    cfg, sd, x, t_mod = R.block_inputs(case["cfg"], grid, case["seed"])
+    ctx = R.case_ctx(case)
+    ref, c0 = R.block_ref(case), R.case_fwd(case, 0)
+    blk = DiTBlock(False, cfg["dim"], cfg["num_heads"], cfg["ffn_dim"], cfg["eps"])
+    blk.load_state_dict(sd, strict=True)
+    blk = blk.to(BF).cuda()
+    rope = RopeTable.from_grid(precompute_freqs_cis_3d(cfg["dim"] // cfg["num_heads"]), *grid, "cuda")
+    seen, real = [], (ops.cross_probs, ops.flash_attn)
+    ops.cross_probs = lambda q, k, *a, **kw: seen.append(("folded", k.shape[0], kw.get("last_key_mult", 1))) or real[0](q, k, *a, **kw)
+    ops.flash_attn = lambda q, k, *a, **kw: seen.append(("attn", k.shape[0], kw.get("last_key_mult", 1))) or real[1](q, k, *a, **kw)
+    memo = {}
+    try:
+        with torch.no_grad(), ops.options(attn_q_prescale=case["prescale"], **opts):
+            out = blk(x.cuda()[None], ctx.cuda()[None], t_mod.cuda(), rope, self_attn_memo=memo)
+    finally:
+        ops.cross_probs, ops.flash_attn = real
+    route, keys, m = R.route_of(cfg["num_heads"], case["L"], R.run_start(ctx), opts.get("fold_pad_keys", True), opts.get("fold_cross_o", True))
+    want = [("attn", x.shape[0], 1), ("folded" if route == "folded" else "attn", keys, m)]
+    stats = R.block_stats(types.SimpleNamespace(out=out[0].cpu(), x1=memo["x"].cpu()), c0, ref)
+    err = max([s["worst"] / R.FWD_ROW_BAR[k] for k, s in stats.items()] +
+              [math.inf if (sorted(seen) != sorted(want) or route != case["cross"] or any(s["zero_bad"] for s in stats.values())) else 0.0])
+    where = max(stats.items(), key=lambda kv: kv[1]["worst"] / R.FWD_ROW_BAR[kv[0]])
+    return (f"infwd {case['cfg']} grid={grid} L={case['L']} p={p} route={route} prescale={case['prescale']} opts={sorted(opts)} calls={seen} | "
+            f"worst {where[0]} {where[1]['where']} {where[1]['worst']:.3f}"), err, 1.0
+
+
+CASES = {"infwd": case_infwd, "tape": case_tape, "gemmpin": case_gemmpin, "vaepin": case_vaepin, "gemm": case_gemm, "attn": case_attn, "rows": case_rows, "cfg": case_cfg, "attnbwd": case_attnbwd, "fp8": case_fp8,
          "batched": case_batched, "misc": case_misc, "bwdrows": case_bwdrows, "fwdrows": case_fwdrows, "attnfwd": case_attnfwd, "crossfold": case_crossfold,
          "sagepin": case_sagepin}
-OPT_IN = ("fwdrows", "attnfwd", "gemmpin", "vaepin", "crossfold", "sagepin", "tape")     # run with --only alone (bwdrows is in the default sweep): the default sweep, and the suite's run of it, stays what it was
+OPT_IN = ("fwdrows", "attnfwd", "gemmpin", "vaepin", "crossfold", "sagepin", "tape", "infwd")     # run with --only alone (bwdrows is in the default sweep): the default sweep, and the suite's run of it, stays what it was
 
 
 def main():
