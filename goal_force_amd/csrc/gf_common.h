@@ -33,6 +33,25 @@ __device__ __forceinline__ unsigned pack2bf(float lo, float hi) {
     return __builtin_bit_cast(unsigned, __builtin_convertvector(f2_t{lo, hi}, b2_t));
 }
 
+// eight bf16 -> their e4m3 bytes in column order, torch's codes (`.to(float8_e4m3fn)`): round to nearest even up to 464 (the tie
+// between 448 and the NaN code rounds down to 448) and NaN above, for +-inf and for NaN.  Whether the conversion instruction saturates
+// or gives NaN there may depend on the wave's overflow mode, so that code is formed here, from the bf16 pattern (464.0 = 0x43E8):
+// sign | 0x7F.  (gf_cast_fp8 and gf_cast_fp8_t.)
+__device__ __forceinline__ u32x2 cast_e4m3_8(const u16x8 v) {
+    unsigned w[2] = {0, 0};
+    w[0] = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(v[0]), bf2f(v[1]), w[0], false);
+    w[0] = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(v[2]), bf2f(v[3]), w[0], true);
+    w[1] = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(v[4]), bf2f(v[5]), w[1], false);
+    w[1] = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(v[6]), bf2f(v[7]), w[1], true);
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+        if ((v[j] & 0x7fffu) > 0x43E8u) {
+            const int sh = (j & 3) * 8;
+            w[j >> 2] = (w[j >> 2] & ~(0xffu << sh)) | ((((unsigned)v[j] >> 8 & 0x80u) | 0x7fu) << sh);
+        }
+    return u32x2{w[0], w[1]};
+}
+
 __device__ __forceinline__ float gelu_tanh_f(float x) {
     // torch GELU(approximate='tanh'): 0.5*x*(1+tanh(sqrt(2/pi)*(x+0.044715*x^3)))
     // = x * sigmoid(2u), u = sqrt(2/pi) * (x + 0.044715 x^3): one exp2 and one rcp instead of the tanhf library call (a GEMM

@@ -488,27 +488,59 @@ __global__ __launch_bounds__(ROW_THREADS) void quant_fp8_rowscale_kernel(const u
     }
 }
 
-// plain bf16 -> e4m3 cast (the weight side of fp8_linear: `weight.to(float8_e4m3fn)`, unit scale, VRAM:138).  torch rounds to nearest
-// even up to 464 (the tie between 448 and the NaN code rounds down to 448) and gives NaN above, for +-inf and for NaN; whether the
-// conversion instruction saturates or gives NaN there may depend on the wave's overflow mode, so that code is formed here, from the
-// bf16 pattern (464.0 = 0x43E8): sign | 0x7F.
+// The gradient quantiser (include/goalforce.h: gf_quant_fp8_grad): a power-of-two scale per row, so that scaling is exact and the
+// codes are the e4m3 rounding of the gradient itself in a shifted exponent window.  One workgroup per row, row kept in registers,
+// as quant_fp8_rowscale_kernel.  |bf16| orders like its 15-bit pattern, so the row maximum is an integer maximum and carries the
+// non-finite test (>= 0x7F80) with it; with the maximum m 2^E (1 <= m < 2) and 448 = 1.75 x 2^8, e = E - 8 + (m > 1.75), at least -126.
+__global__ __launch_bounds__(ROW_THREADS) void quant_fp8_grad_kernel(const u16* __restrict__ x, unsigned char* __restrict__ out,
+                                                                     float* __restrict__ scale, int dim, long x_stride,
+                                                                     long out_stride) {
+    __shared__ unsigned red[ROW_THREADS / 64];
+    const long row = blockIdx.x;
+    const int tid = threadIdx.x;
+    const int nchunks = dim >> 3;
+    const u16* xr = x + row * x_stride;
+    constexpr int NCH = 14;  // dim <= 128*14*8 = 14336 (FFN hidden 13824)
+    u16x8 v[NCH];
+    unsigned mx = 0;
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+        const int c = tid + i * ROW_THREADS;
+        if (c < nchunks) {
+            v[i] = *reinterpret_cast<const u16x8*>(xr + (c << 3));
+#pragma unroll
+            for (int j = 0; j < 8; ++j) mx = max(mx, (unsigned)v[i][j] & 0x7fffu);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = max(mx, (unsigned)__shfl_xor((int)mx, o));
+    if ((tid & 63) == 0) red[tid >> 6] = mx;
+    __syncthreads();
+    mx = max(red[0], red[1]);
+    const bool bad = mx >= 0x7f80u;                          // an inf or a NaN in the row: scale NaN, codes 0x00
+    const int e = mx == 0 ? 0 : max((int)(mx >> 7) - 135 + (int)((mx & 0x7fu) > 0x60u), -126);       // <= 120: 2^e and 2^-e are normal
+    if (tid == 0) scale[row] = __uint_as_float(bad ? 0x7fc00000u : (unsigned)(e + 127) << 23);
+    const float inv = __uint_as_float((unsigned)(127 - e) << 23);   // x 2^-e is exact (or below 2^-126, which e4m3 rounds to +-0)
+    unsigned char* orow = out + row * out_stride;
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+        const int c = tid + i * ROW_THREADS;
+        if (c < nchunks) {
+            float f[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) f[j] = bf2f(v[i][j]) * inv;
+            const u32x2 w = Fp8RowScale::pack(f);
+            *reinterpret_cast<u32x2*>(orow + (c << 3)) = bad ? u32x2{0u, 0u} : w;
+        }
+    }
+}
+
+// plain bf16 -> e4m3 cast (the weight side of fp8_linear: `weight.to(float8_e4m3fn)`, unit scale, VRAM:138): torch's codes on every
+// input (cast_e4m3_8).
 __global__ __launch_bounds__(256) void cast_fp8_kernel(const u16* __restrict__ x, unsigned char* __restrict__ out, long n8) {
     const long stride = (long)gridDim.x * 256;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n8; i += stride) {
-        const u16x8 v = reinterpret_cast<const u16x8*>(x)[i];
-        unsigned w[2] = {0, 0};
-        w[0] = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(v[0]), bf2f(v[1]), w[0], false);
-        w[0] = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(v[2]), bf2f(v[3]), w[0], true);
-        w[1] = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(v[4]), bf2f(v[5]), w[1], false);
-        w[1] = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(v[6]), bf2f(v[7]), w[1], true);
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            if ((v[j] & 0x7fffu) > 0x43E8u) {
-                const int sh = (j & 3) * 8;
-                w[j >> 2] = (w[j >> 2] & ~(0xffu << sh)) | ((((unsigned)v[j] >> 8 & 0x80u) | 0x7fu) << sh);
-            }
-        reinterpret_cast<u32x2*>(out)[i] = u32x2{w[0], w[1]};
-    }
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n8; i += stride)
+        reinterpret_cast<u32x2*>(out)[i] = cast_e4m3_8(reinterpret_cast<const u16x8*>(x)[i]);
 }
 
 }  // namespace
@@ -524,6 +556,22 @@ extern "C" GF_API int gf_quant_fp8_rowscale(const void* x, void* out8, float* sc
     hipLaunchKernelGGL(quant_fp8_rowscale_kernel, dim3((unsigned)rows), dim3(ROW_THREADS), 0, (hipStream_t)stream,
                        (const u16*)x, (unsigned char*)out8, scale, (int)dim, (long)x_stride, (long)out_stride);
     GF_CHECK_LAUNCH("gf_quant_fp8_rowscale");
+    return GF_OK;
+}
+
+extern "C" GF_API int gf_quant_fp8_grad(const void* x, void* out8, float* scale, int64_t rows, int64_t dim,
+                                        int64_t x_stride, int64_t out_stride, void* stream) {
+    GF_CHECK_ARG(x && out8 && scale && rows >= 0, "gf_quant_fp8_grad: null pointer");
+    GF_CHECK_ARG(dim > 0 && dim % 8 == 0 && dim <= ROW_THREADS * 14 * 8, "gf_quant_fp8_grad: dim=%ld must be a multiple of 8 and <= %d",
+                 (long)dim, ROW_THREADS * 14 * 8);
+    GF_CHECK_ARG(x_stride >= dim && out_stride >= dim, "gf_quant_fp8_grad: row strides %ld / %ld below dim=%ld", (long)x_stride,
+                 (long)out_stride, (long)dim);
+    GF_CHECK_ARG(x_stride % 8 == 0 && out_stride % 8 == 0 && gf_aligned16(x) && (((uintptr_t)out8) & 7u) == 0,
+                 "gf_quant_fp8_grad: alignment");
+    if (rows == 0) return GF_OK;
+    hipLaunchKernelGGL(quant_fp8_grad_kernel, dim3((unsigned)rows), dim3(ROW_THREADS), 0, (hipStream_t)stream,
+                       (const u16*)x, (unsigned char*)out8, scale, (int)dim, (long)x_stride, (long)out_stride);
+    GF_CHECK_LAUNCH("gf_quant_fp8_grad");
     return GF_OK;
 }
 

@@ -375,6 +375,33 @@ __global__ __launch_bounds__(VT) void transpose_pad64_kernel(const u16* __restri
     }
 }
 
+// out8[k, n] = e4m3(w[n, k]) (gf_cast_fp8_t: the transposed e4m3 weight copy of the fp8 dX GEMM), 64 x 64 tiles through LDS.  A lane
+// loads 16 bytes along K (8 bf16 of one weight row), casts them (cast_e4m3_8: gf_cast_fp8's codes) and scatters the 8 bytes down a
+// column of the byte tile [k][n]; a lane then stores 16 bytes along N of one output row.  Pitch 68 bytes = 17 dwords: the 8 lanes of a
+// weight row's chunks write 8 x 17 dwords apart (banks 8 apart), the 8 rows beside them share two dwords.  N % 64 == 0 (the launcher
+// asks % 128), K % 8 == 0: a tile is full along n and cut at whole chunks along k.
+constexpr int CT_PITCH = 68;
+__global__ __launch_bounds__(VT) void cast_fp8_t_kernel(const u16* __restrict__ w, long ldw, unsigned char* __restrict__ out, long ldo, int K) {
+    __shared__ __attribute__((aligned(16))) unsigned char tile[64 * CT_PITCH];
+    const int t = threadIdx.x;
+    const int n0 = blockIdx.x * 64, k0 = blockIdx.y * 64;
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+        const int row = (t >> 3) + 32 * it, ch = t & 7;           // weight row n0 + row, columns k0 + 8 ch ..
+        if (k0 + 8 * ch < K) {
+            const u32x2 c = cast_e4m3_8(*reinterpret_cast<const u16x8*>(w + (long)(n0 + row) * ldw + k0 + 8 * ch));
+#pragma unroll
+            for (int e = 0; e < 8; ++e) tile[(8 * ch + e) * CT_PITCH + row] = (unsigned char)(c[e >> 2] >> (8 * (e & 3)));
+        }
+    }
+    __syncthreads();
+    const int kr = t >> 2, ch = t & 3;                            // output row k0 + kr, bytes n0 + 16 ch ..
+    if (k0 + kr < K) {
+        const unsigned* src = reinterpret_cast<const unsigned*>(tile + kr * CT_PITCH + 16 * ch);
+        *reinterpret_cast<u32x4*>(out + (long)(k0 + kr) * ldo + n0 + 16 * ch) = u32x4{src[0], src[1], src[2], src[3]};
+    }
+}
+
 // nn.Upsample(scale_factor=(2, 2), mode="nearest-exact") (VAE:82-96) of a contiguous [T, H, W, C] activation, written into the
 // INTERIOR of a zero-bordered buffer [T][2 H + 2][2 W + 2][C] (the input layout of gf_conv3d_padded_bf16 with kt = 1): source pixel
 // (t, y, x) goes to the four pixels (2 y + a, 2 x + b).  One thread per 16-byte chunk of a source pixel.
@@ -597,6 +624,19 @@ extern "C" GF_API int gf_transpose_pad_batched(const void* src, int64_t ld_src, 
     GF_CHECK_ARG(src && dst && R > 0 && C > 0 && rpad >= R && ld_src >= C && batch > 0 && batch < 65536 && stride_src >= 0 &&
                      stride_dst >= C * rpad, "gf_transpose_pad_batched: bad arguments");
     return transpose_pad_launch("gf_transpose_pad_batched", src, ld_src, stride_src, dst, stride_dst, R, C, rpad, batch, stream);
+}
+
+extern "C" GF_API int gf_cast_fp8_t(const void* w, int64_t ldw, void* out8, int64_t ldo, int64_t N, int64_t K, void* stream) {
+    GF_CHECK_ARG(w && out8, "gf_cast_fp8_t: null pointer");
+    GF_CHECK_ARG(N > 0 && N % 128 == 0 && K > 0 && K % 8 == 0 && K <= 64 * 65535L,
+                 "gf_cast_fp8_t: N=%ld must be a multiple of 128 (it is the GEMM's K) and K=%ld a multiple of 8", (long)N, (long)K);
+    GF_CHECK_ARG(ldw >= K && ldw % 8 == 0 && ldo >= N && ldo % 16 == 0, "gf_cast_fp8_t: ldw=%ld must be >= K and a multiple of 8, ldo=%ld >= N and a multiple of 16",
+                 (long)ldw, (long)ldo);
+    GF_CHECK_ARG(gf_aligned16(w) && gf_aligned16(out8), "gf_cast_fp8_t: alignment");
+    hipLaunchKernelGGL(cast_fp8_t_kernel, dim3((unsigned)(N / 64), (unsigned)((K + 63) / 64)), dim3(VT), 0, (hipStream_t)stream, (const u16*)w,
+                       (long)ldw, (unsigned char*)out8, (long)ldo, (int)K);
+    GF_CHECK_LAUNCH("gf_cast_fp8_t");
+    return GF_OK;
 }
 
 extern "C" GF_API int gf_vae_tile_blend(void* values, void* weight, const void* tile, int64_t nch, int64_t T, int64_t th,

@@ -181,6 +181,18 @@ fp8_weight = functools.partial(weight_copy, kind="fp8")    # the layer's current
 fp4_weight = functools.partial(weight_copy, kind="fp4")    # ... MXFP4 copy (enable_fp4) as (packed e2m1 codes, E8M0 scales), or None
 
 
+def fp8_weight_t(lin: nn.Linear):
+    """The transposed e4m3 copy `_gf_w8t` [in_features, out_features] of an enable_fp8 layer (ops.cast_fp8_t): the weight operand of
+    dX = dY · W8 on ops.gemm_fp8 (training.linear_dx_fp8).  Cached under param_key(lin.weight) exactly as weight_copy caches `_gf_w8`,
+    but made lazily, on the first backward — inference never pays its byte per parameter — and dropped by enable_fp8(module, False)."""
+    if getattr(lin, "_gf_w8", None) is None:
+        raise GoalForceError("fp8_weight_t: the layer carries no fp8 copy: call enable_fp8 first")
+    key = param_key(lin.weight)
+    if getattr(lin, "_gf_w8t", None) is None or lin._gf_w8t_key != key:
+        lin._gf_w8t, lin._gf_w8t_key = ops.cast_fp8_t(lin.weight.detach()), key
+    return lin._gf_w8t
+
+
 class QuantizedInput:
     """A quantised activation shared by the GEMMs that read the same input: `kind` "fp8" — `data` e4m3 bytes, `scale` fp32 per row;
     "fp4" — MXFP4, `data` packed e2m1 codes, `scale` E8M0 bytes (what ops.layernorm_modulate_mxfp4 / ops.gemm_mxfp4_q4 return)."""
@@ -245,6 +257,8 @@ def enable_fp8(module: nn.Module, enabled=True):
     for blk in (m for m in module.modules() if isinstance(m, DiTBlock)):
         for lin in (m for m in blk.modules() if isinstance(m, nn.Linear)):
             weight_copy(lin, "fp8", bool(enabled))
+            if not enabled and getattr(lin, "_gf_w8t", None) is not None:
+                lin._gf_w8t = lin._gf_w8t_key = None      # the backward's transposed copy (fp8_weight_t) goes with it
     return module
 
 
@@ -319,12 +333,20 @@ def enable_sparse_attention(module: nn.Module, pattern, dense_blocks: int = 0):
     return module
 
 
-def refuse_training(block: "DiTBlock"):
-    """What training.DiTBlockFn refuses of a block's switches, before its forward runs."""
+def refuse_training(block: "DiTBlock", fp8_frozen: bool = False):
+    """What training.DiTBlockFn refuses of a block's switches, before its forward runs.  `fp8_frozen` (training.set_fp8_frozen): an
+    enable_fp8 block is accepted when it is frozen — no parameter requires grad, no live adapter: its backward needs dX alone, which
+    runs on the fp8 GEMM (training.linear_dx_fp8) — and refused by its first trainable parameter's name otherwise."""
     # the backward recomputes the block on the bf16 kernels: an fp8 / fp4 forward would not be the function differentiated
     for kind in ("fp8", "fp4"):      # (in this order, whichever of the two wins on a layer that carries both)
-        if any(precision(m, (kind,)) == kind for m in block.modules()):
+        if any(precision(m, (kind,)) == kind for m in block.modules()) and not (kind == "fp8" and fp8_frozen):
             raise GoalForceError(f"training through an enable_{kind} block is refused: call enable_{kind}(module, False) first")
+    if fp8_frozen and any(precision(m, ("fp8",)) == "fp8" for m in block.modules()):
+        what = next((f"the trainable parameter {n}" for n, p in block.named_parameters() if p.requires_grad), None) or next(
+            (f"a live LoRA adapter ({n}: {lora.live(m)[0].name!r})" for n, m in block.named_modules() if lora.live(m)), None)
+        if what is not None:
+            raise GoalForceError(f"training through an enable_fp8 block is open to frozen blocks only (no weight gradient exists on the fp8 "
+                                 f"kernels): this block has {what}: freeze it, or call enable_fp8(module, False) first")
     for name, m in block.named_modules():
         # a frozen attached adapter would be in the forward only; one made by lora.add_trainable is differentiated (training.DiTBlockFn)
         frozen = [ad for ad in lora.live(m) if not ad.trainable]

@@ -1654,6 +1654,26 @@ def cast_fp8(w):
     return out
 
 
+def quant_fp8_grad(x):
+    """A gradient x [M,K] bf16 (rows may be strided) -> (x8 [M,K] float8_e4m3fn, scale [M] fp32, a power of two per row) —
+    gf_quant_fp8_grad: x8 = e4m3(x / scale) with the division exact; an inf / NaN row gives scale NaN."""
+    _req(x, "quant_fp8_grad.x")
+    xv, rows, dim, xs = _rows2d(x, "quant_fp8_grad.x")
+    out = torch.empty((rows, dim), dtype=_FP8, device=x.device)
+    scale = torch.empty((rows,), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.load().gf_quant_fp8_grad(_ptr(xv), _ptr(out), _ptr(scale), rows, dim, xs, dim, _stream(x)), "gf_quant_fp8_grad")
+    return out, scale
+
+
+def cast_fp8_t(w):
+    """w [N,K] bf16 (contiguous rows) -> [K,N] float8_e4m3fn, cast_fp8(w).t() made in one pass — gf_cast_fp8_t; N % 128 == 0, K % 8 == 0."""
+    _mat(w, "cast_fp8_t.w")
+    N, K = w.shape
+    out = torch.empty((K, N), dtype=_FP8, device=w.device)
+    _lib.check(_lib.load().gf_cast_fp8_t(_ptr(w), w.stride(0), _ptr(out), N, N, K, _stream(w)), "gf_cast_fp8_t")
+    return out
+
+
 def gemm_fp8(a8, row_scale, w8, bias=None, epilogue=EPI_BIAS, resid=None, gate=None, out=None):
     """out[M,N] = epilogue((a8 @ w8^T) * row_scale[:,None] + bias) — gf_gemm_fp8."""
     if row_scale is None:

@@ -17,6 +17,8 @@ Design (MI355X-first, not a port of torch autograd):
     a forward + an activation-only backward); GEMM backward reuses the forward GEMM on transposed operands
     (dX = dY W via W^T; dW = dY^T X via dY^T, X^T padded to the K step).
   * gradient fan-in (a tensor used twice) is summed by the HIP add kernel inside the Functions, not by autograd.
+  * set_fp8_frozen(True): frozen enable_fp8 blocks (the experts under `--enable_fp8_training`) run forward, recompute and dX on the
+    fp8 GEMM (linear_dx_fp8: dY quantised per row on a power-of-two scale, the weight's transposed e4m3 copy); off by default.
 """
 from __future__ import annotations
 
@@ -29,7 +31,7 @@ import torch.nn as nn
 
 from . import lora, ops
 from ._lib import GoalForceError
-from .dit import DiTBlock, RopeTable, WanModel, _tokens2d, q_rotation, refuse_training
+from .dit import DiTBlock, QuantizedInput, RopeTable, WanModel, _tokens2d, fp8_weight_t, precision, q_rotation, refuse_training
 from .dit import linear as dit_linear
 
 BF = torch.bfloat16
@@ -52,6 +54,26 @@ def linear_dx(dy: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
         raise GoalForceError(f"linear_dx: out_features={n} must be a multiple of 64")
     w_t = ops.transpose_pad(weight.detach(), n)              # [K, N]
     return ops.gemm(dy, w_t, None)
+
+
+def linear_dx_fp8(dy: torch.Tensor, lin: nn.Linear) -> torch.Tensor:
+    """dX[M,K] = dY[M,N] W8[N,K] of an enable_fp8 layer on the fp8 GEMM: dY quantised per row with a power-of-two scale
+    (ops.quant_fp8_grad), the weight the layer's transposed e4m3 copy (dit.fp8_weight_t; out_features must be a multiple of 128)."""
+    return ops.gemm_fp8(*ops.quant_fp8_grad(dy), fp8_weight_t(lin))
+
+
+# Frozen enable_fp8 blocks on the tape (set_fp8_frozen): off, DiTBlockFn refuses every enable_fp8 block, as it always has.
+FP8_FROZEN = False
+
+
+def set_fp8_frozen(on: bool) -> bool:
+    """Open the tape to FROZEN enable_fp8 blocks (a frozen expert under a bf16 ControlNet): their forward is the fp8 inference forward
+    and their backward takes dX = dY W8 on the fp8 GEMM (DiTBlockFn).  An fp8 block with a trainable parameter or a live adapter stays
+    refused, and so do fp4, sage and sparse blocks (dit.refuse_training).  Returns the setting that was in force.  A call, like
+    set_keep_level: nothing reads the environment."""
+    global FP8_FROZEN
+    old, FP8_FROZEN = FP8_FROZEN, bool(on)
+    return old
 
 
 def linear_dw(dy: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
@@ -261,12 +283,16 @@ class DiTBlockFn(torch.autograd.Function):
     y + s * (x A^T) B^T is differentiated beside the layer —
         t = bf16(x A^T), dt = bf16(dy B);  dB = s dy^T t,  dA = s dt^T x  (ops.lora_grad: one pass over dy / x each);
         dx = dx_base + s dt A  (ops.lora_up on the base layer's dx, in place)
-    with s applied in these three consumers and never to dy (no extra pass over [M, N])."""
+    with s applied in these three consumers and never to dy (no extra pass over [M, N]).
+    A frozen enable_fp8 block (set_fp8_frozen): the forward is the fp8 inference forward, and what is differentiated is that forward
+    with a straight-through activation quantiser — the quantiser's gradient is the identity and every Linear's is dX = dY W8, W8 the
+    layer's e4m3 copy (not the bf16 master): linear_dx_fp8, with dY quantised per row on a power-of-two scale.  The recompute runs the
+    same fp8 kernels on the same inputs as the forward (dit.linear), so at every keep level it rebuilds the forward's own bits."""
 
     @staticmethod
     def forward(ctx, block, rope, x2, ctx2, t_mod, *params):
         ctx.block, ctx.rope = block, rope
-        refuse_training(block)
+        refuse_training(block, FP8_FROZEN)
         ctx.adapters = _block_adapters(block)
         if len(params) != len(_PARAM_NAMES) + 2 * len(ctx.adapters):
             raise GoalForceError(f"DiTBlockFn: {len(params)} parameters for a block with {len(ctx.adapters)} live trainable adapters: "
@@ -318,7 +344,7 @@ class DiTBlockFn(torch.autograd.Function):
                 g[prefix + ".weight"] = linear_dw(dy, xin)
             if need[prefix + ".bias"]:
                 g[prefix + ".bias"] = bias_grad(dy)
-            dx = linear_dx(dy, layer.weight) if want_dx else None
+            dx = (linear_dx_fp8(dy, layer) if precision(layer) == "fp8" else linear_dx(dy, layer.weight)) if want_dx else None
             for i, ad in by_layer.get(prefix, ()):
                 need_a, need_b = ctx.lora_needs[2 * i], ctx.lora_needs[2 * i + 1]
                 if not (want_dx or need_a or need_b):
@@ -338,7 +364,11 @@ class DiTBlockFn(torch.autograd.Function):
         # is, and what would only feed a parameter gradient nobody asked for (a frozen block) is not computed
         mod = ops.modulation(block.modulation, t_mod.contiguous(), onep_mask=0b010010)
         need_h1 = wide is None or any(need[f"self_attn.{n}.weight"] or f"self_attn.{n}" in by_layer for n in "qkv")
-        h1 = ops.layernorm_modulate(x, scale1p=mod[1], shift=mod[0], eps=eps) if need_h1 else None
+        fp8 = precision(sa.q) == "fp8"       # a frozen enable_fp8 block: one quantisation of h1 for q / k / v, as the forward's (never bf16 in HBM)
+        if fp8 and need_h1:
+            h1 = QuantizedInput.layernorm(x, "fp8", scale1p=mod[1], shift=mod[0], eps=eps)
+        else:
+            h1 = ops.layernorm_modulate(x, scale1p=mod[1], shift=mod[0], eps=eps) if need_h1 else None
         if wide is not None:
             qp, kp, vv = wide["qp"], wide["kp"], wide["v"]
         else:
@@ -351,7 +381,8 @@ class DiTBlockFn(torch.autograd.Function):
         o = lin(a, sa.o) if (wide is None or need["modulation"]) else None            # o: x1 (unless kept) and the gate's gradient
         x1 = wide["x1"] if wide is not None else ops.add(x, ops.colsum(o, gate=mod[2]))   # x + gate_msa * o
         h2 = ops.layernorm_modulate(x1, weight=block.norm3.weight, bias=block.norm3.bias, eps=eps)
-        q2p, k2p, v2 = lin(h2, ca.q), lin(c2, ca.k), lin(c2, ca.v)
+        c2q = QuantizedInput(c2) if precision(ca.k) == "fp8" else c2          # (the forward's one quantisation of the context)
+        q2p, k2p, v2 = lin(h2, ca.q), lin(c2q, ca.k), lin(c2q, ca.v)
         q2n, k2n = q2p.clone(), k2p.clone()
         ops.rmsnorm_rope(q2n, ca.norm_q.weight, None, None, hd, ca.norm_q.eps)
         ops.rmsnorm_rope(k2n, ca.norm_k.weight, None, None, hd, ca.norm_k.eps)

@@ -672,6 +672,28 @@ GF_API int gf_linear_vt32_fp8(const void* x8, int64_t ldx, const float* x_scale,
  * nearest even, |x| <= 464 -> at most 448, |x| > 464, +-inf and NaN -> the NaN code (sign | 0x7F): no saturation. */
 GF_API int gf_cast_fp8(const void* x, void* out8, int64_t n, void* stream);
 
+/* Training through FROZEN fp8 layers (training.set_fp8_frozen; no weight gradient): dX = dY · W8 on gf_gemm_fp8, from the two below.
+ *
+ * gf_quant_fp8_grad — the per-row quantiser of a GRADIENT, with a power-of-two scale (gf_quant_fp8_rowscale's clamp(min=1) would turn a
+ * row of magnitude 1e-5 into zeros).  x [rows, dim] bf16 (rows may be strided) -> out8 [rows, dim] e4m3 bytes, scale [rows] fp32;
+ * dim % 8 == 0, dim <= 14336, strides >= dim and % 8 == 0.  Per row, with amax = max|x|:
+ *   e      the smallest integer with amax 2^-e <= 448, clamped to [-126, 127]
+ *   scale  2^e;   out8 = e4m3(x 2^-e), round to nearest even as gf_cast_fp8 rounds.  The product is exact in fp32 (a power of two; what
+ *          underflows fp32 is far below e4m3's half step and rounds to +-0 either way), so there is ONE rounding, the codes are the
+ *          e4m3 rounding of the gradient itself in a shifted exponent window, |x 2^-e| <= 448 never gives the NaN code, and the GEMM
+ *          epilogue's `* row_scale` adds no rounding.
+ *   zero row (amax == 0)                e = 0, the cast's codes of +-0 (0x00 / 0x80)
+ *   a row holding an inf or a NaN       scale = NaN and all codes 0x00: that row of the GEMM comes out NaN, never silently zero
+ * Nothing outside [rows, dim] of either output is written. */
+GF_API int gf_quant_fp8_grad(const void* x, void* out8, float* scale, int64_t rows, int64_t dim,
+                             int64_t x_stride, int64_t out_stride, void* stream);
+
+/* gf_cast_fp8_t — the transposed e4m3 weight copy, made once per weight: w [N, K] bf16 (row pitch ldw) -> out8 [K, N] e4m3 bytes (row
+ * pitch ldo), out8[k, n] bit for bit what gf_cast_fp8 makes of w[n, k] (the NaN code above 464 included) — the [N', K'] operand of
+ * gf_gemm_fp8 with the layer's out_features as the reduction dimension.  N % 128 == 0 (N becomes the GEMM's K), K % 8 == 0,
+ * ldw % 8 == 0, ldw >= K, ldo % 16 == 0, ldo >= N, both pointers 16-byte aligned.  Bytes [N, ldo) of an output row are not written. */
+GF_API int gf_cast_fp8_t(const void* w, int64_t ldw, void* out8, int64_t ldo, int64_t N, int64_t K, void* stream);
+
 /* gf_gemm_fp8 — C = epilogue((A8 · W8^T) * row_scale[m] + bias); A8 [M,K], W8 [N,K] e4m3 bytes (K contiguous),
  * fp32 accumulate on v_mfma_f32_16x16x128_f8f6f4 (2x the bf16 MFMA rate; M >= 512: the 4-wave asm K loop).  As MEASURED through
  * these kernels on an MI355X (no vendor statement; model: tests/gemm_refs.py::mfma_fp8, held by tests/test_gemm_pinned_gpu.py::

@@ -47,9 +47,14 @@ def check_args(args):
         raise NotImplementedError("strided ControlNet is not used by Goal Force")
     if args.control_signal_type not in ("canny_edge", "direct_force_and_goal_force_and_mass"):
         raise NotImplementedError(args.control_signal_type)                                            # train.py:33-38
-    if getattr(args, "enable_fp8_training", False):
-        raise NotImplementedError("--enable_fp8_training: trainable LoRA adapters run on bf16 layers only (the backward recomputes the block in bf16)")
     trainable = args.trainable_models or ""
+    if getattr(args, "enable_fp8_training", False):
+        # the experts' blocks run fp8 and frozen (training.set_fp8_frozen: dX on the fp8 GEMM, no weight gradient); nothing of them may train
+        if args.lora_base_model is not None:
+            raise NotImplementedError("--enable_fp8_training: trainable LoRA adapters run on bf16 layers only (the fp8 tape is open to frozen "
+                                      "blocks: drop --lora_base_model)")
+        if any(m in ("dit", "dit2") for m in trainable.split(",")):
+            raise NotImplementedError("--enable_fp8_training: the experts run fp8 and frozen: --trainable_models may not name dit or dit2")
     if args.lora_base_model is None:
         if args.lora_checkpoint is not None:
             raise NotImplementedError("--lora_checkpoint needs --lora_base_model (the reference ignores it without one; here it is an error)")
@@ -80,6 +85,29 @@ def add_lora(pipe, args):
     return n
 
 
+def parser():
+    """wan_parser (the reference's command line, pinned argument for argument) plus `--enable_fp8_training`, which the reference passes
+    to its training module rather than its parser (train.py:42, 51, 62: computation in float8_e4m3fn over the frozen base)."""
+    from goal_force_amd.training import wan_parser
+    ap = wan_parser()
+    ap.add_argument("--enable_fp8_training", default=False, action="store_true",
+                    help="Run the frozen experts' blocks on the fp8 kernels, forward and backward (ControlNet training only).")
+    return ap
+
+
+def enable_fp8_training(pipe, args):
+    """`--enable_fp8_training`: enable_fp8 on both experts (frozen by freeze_except: check_args lets no expert train beside the flag)
+    and the tape opened to frozen fp8 blocks.  -> the number of experts switched."""
+    if not getattr(args, "enable_fp8_training", False):
+        return 0
+    from goal_force_amd import dit, training
+    experts = [m for m in (getattr(pipe, "dit", None), getattr(pipe, "dit2", None)) if m is not None]
+    for m in experts:
+        dit.enable_fp8(m)
+    training.set_fp8_frozen(True)
+    return len(experts)
+
+
 class WanTrainingModule:
     """train.py:12-124 around the HIP pipeline: what launch_training_task needs of it (`.pipe`, `.extra_inputs`, the timestep
     boundaries)."""
@@ -96,6 +124,7 @@ class WanTrainingModule:
         self.pipe.scheduler.set_timesteps(1000, training=True)                                             # utils.py:560
         self.pipe.freeze_except([] if args.trainable_models is None else args.trainable_models.split(","))   # utils.py:563
         add_lora(self.pipe, args)                                                                          # utils.py:569-584
+        enable_fp8_training(self.pipe, args)
         if args.controlnet_checkpoint is not None:                                                        # utils.py:586-590
             self.pipe.load_controlnet_weights(self.pipe.controlnet, args.controlnet_checkpoint, torch_dtype=torch.bfloat16)
             print(f"ControlNet checkpoint loaded: {args.controlnet_checkpoint}, total {len(self.pipe.controlnet.state_dict())} keys")
@@ -107,7 +136,7 @@ class WanTrainingModule:
 
 def main(argv=None):
     from goal_force_amd import training as tr
-    args = tr.wan_parser().parse_args(argv)
+    args = parser().parse_args(argv)
     import torch
     from goal_force_amd.distributed import init_from_env
     rank, local, world = init_from_env()
