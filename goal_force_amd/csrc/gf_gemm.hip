@@ -73,6 +73,15 @@ struct GemmArgs {
     int rsv2 = 0;
 };
 
+// gf_gemm_fp8_lora (gemm_a4_kernel<EPI, true, LORA>): the arguments of the product plus one attached adapter's operands.  A struct of
+// its own, so that the kernarg of every other instantiation stays the GemmArgs it was scheduled and measured with.
+struct GemmLoraArgs : GemmArgs {
+    const u16* T = nullptr;    // t = bf16(x down^T) [M, ldt]
+    const u16* U = nullptr;    // up [N, ld_up], zero past the true rank
+    long ldt = 0, ld_up = 0;
+    float scale = 0.f;
+};
+
 // internal epilogue of gf_linear_vt32 (not in goalforce.h's enum): C rows = output features, C columns = keys in kernel 3's
 // order, bias per ROW, columns >= wrows zero
 constexpr int GF_EPI_VT32 = 6;
@@ -704,8 +713,50 @@ constexpr int A4_THREADS = 256;
 // 128 bytes per row (= 128 elements, one k step of v_mfma_f32_16x16x128_f8f6f4), the loop is gf_gemm_a4f8_loop.inc (two barriers
 // per tile, staging by half tiles: tools/gen_gemm_a4f8.py) and the epilogue multiplies each row by its activation scale first.
 // p.lda / p.ldw / p.K are in ELEMENTS of the operand type.
-template <int EPI, bool FP8 = false>
-__global__ __launch_bounds__(A4_THREADS, 1) void gemm_a4_kernel(const GemmArgs p) {
+// The adapter's MFMAs of one column block j (gemm_a4_kernel<EPI, true, LORA>): d[i] = sum over the LORA chunks of 32 rank columns of
+// u[ch] (A: 16 rows of `up`) x t[i][ch] (B: 16 rows of `t`), i < 8, from a zero accumulator, chunks ascending.  One asm statement with
+// VGPR operands throughout: between the K loop and the last accumulator read the AGPRs are the loop's (tools/check_a4_agpr.py), and the
+// builtin's result would be placed there.  The waits the compiler would add are written out: eight independent MFMAs of 8 passes each
+// stand between a chunk-0 MFMA and the chunk-1 MFMA that reads its result as SrcC, and the closing nops (24 wait states) cover the
+// last MFMA's result against the VALU reads, and its operands against the loads, that follow the statement.
+template <int LORA>
+__device__ __forceinline__ void a4_lora_mfma(f32x4 (&d)[8], const u16x8 (&u)[LORA], const u16x8 (&t)[8][LORA]) {
+    static_assert(LORA == 1 || LORA == 2, "rank_pad 32 or 64");
+#define GF_LORA_MFMA8(c, u_, t0) \
+    "v_mfma_f32_16x16x32_bf16 %0, " u_ ", " t0 "0], " c "0\n\tv_mfma_f32_16x16x32_bf16 %1, " u_ ", " t0 "1], " c "1\n\t" \
+    "v_mfma_f32_16x16x32_bf16 %2, " u_ ", " t0 "2], " c "2\n\tv_mfma_f32_16x16x32_bf16 %3, " u_ ", " t0 "3], " c "3\n\t" \
+    "v_mfma_f32_16x16x32_bf16 %4, " u_ ", " t0 "4], " c "4\n\tv_mfma_f32_16x16x32_bf16 %5, " u_ ", " t0 "5], " c "5\n\t" \
+    "v_mfma_f32_16x16x32_bf16 %6, " u_ ", " t0 "6], " c "6\n\tv_mfma_f32_16x16x32_bf16 %7, " u_ ", " t0 "7], " c "7\n\t"
+#define GF_LORA_MFMA8_ZERO(u_, t0) \
+    "v_mfma_f32_16x16x32_bf16 %0, " u_ ", " t0 "0], 0\n\tv_mfma_f32_16x16x32_bf16 %1, " u_ ", " t0 "1], 0\n\t" \
+    "v_mfma_f32_16x16x32_bf16 %2, " u_ ", " t0 "2], 0\n\tv_mfma_f32_16x16x32_bf16 %3, " u_ ", " t0 "3], 0\n\t" \
+    "v_mfma_f32_16x16x32_bf16 %4, " u_ ", " t0 "4], 0\n\tv_mfma_f32_16x16x32_bf16 %5, " u_ ", " t0 "5], 0\n\t" \
+    "v_mfma_f32_16x16x32_bf16 %6, " u_ ", " t0 "6], 0\n\tv_mfma_f32_16x16x32_bf16 %7, " u_ ", " t0 "7], 0\n\t"
+    if constexpr (LORA == 1) {
+        asm volatile("s_nop 3\n\t" GF_LORA_MFMA8_ZERO("%[u0]", "%[a") "s_nop 7\n\ts_nop 7\n\ts_nop 7"
+                     : "=&v"(d[0]), "=&v"(d[1]), "=&v"(d[2]), "=&v"(d[3]), "=&v"(d[4]), "=&v"(d[5]), "=&v"(d[6]), "=&v"(d[7])
+                     : [u0] "v"(u[0]), [a0] "v"(t[0][0]), [a1] "v"(t[1][0]), [a2] "v"(t[2][0]), [a3] "v"(t[3][0]), [a4] "v"(t[4][0]),
+                       [a5] "v"(t[5][0]), [a6] "v"(t[6][0]), [a7] "v"(t[7][0]));
+    } else {
+        asm volatile("s_nop 3\n\t" GF_LORA_MFMA8_ZERO("%[u0]", "%[a") GF_LORA_MFMA8("%", "%[u1]", "%[b") "s_nop 7\n\ts_nop 7\n\ts_nop 7"
+                     : "=&v"(d[0]), "=&v"(d[1]), "=&v"(d[2]), "=&v"(d[3]), "=&v"(d[4]), "=&v"(d[5]), "=&v"(d[6]), "=&v"(d[7])
+                     : [u0] "v"(u[0]), [a0] "v"(t[0][0]), [a1] "v"(t[1][0]), [a2] "v"(t[2][0]), [a3] "v"(t[3][0]), [a4] "v"(t[4][0]),
+                       [a5] "v"(t[5][0]), [a6] "v"(t[6][0]), [a7] "v"(t[7][0]), [u1] "v"(u[1]), [b0] "v"(t[0][1]), [b1] "v"(t[1][1]),
+                       [b2] "v"(t[2][1]), [b3] "v"(t[3][1]), [b4] "v"(t[4][1]), [b5] "v"(t[5][1]), [b6] "v"(t[6][1]), [b7] "v"(t[7][1]));
+    }
+#undef GF_LORA_MFMA8
+#undef GF_LORA_MFMA8_ZERO
+}
+
+// LORA = n > 0 (gf_gemm_fp8_lora; FP8 only): one attached adapter of rank_pad = 32 n rides the epilogue.  After the K loop every 16 x 16
+// accumulator fragment (i, j) gets its own d = sum_j t[m, j] up[n, j] from n v_mfma_f32_16x16x32_bf16 — A = the fragment's 16 rows of
+// `up`, B = its 16 rows of `t`, so d lands in the accumulator's own lane layout; chunks ascending from a zero accumulator, lane group
+// q holding rank columns 32 ch + 8 q .. + 7: the summation gf_lora_up makes — and the lane continues with
+// bf16(bf16(acc * row_scale + bias) + bf16(scale * bf16(d))) where the plain kernel continues with acc * row_scale + bias: the bits of
+// gf_gemm_fp8(GF_EPI_BIAS) followed by gf_lora_up, without y0's trip through HBM.
+template <int EPI, bool FP8 = false, int LORA = 0>
+__global__ __launch_bounds__(A4_THREADS, 1) void gemm_a4_kernel(const std::conditional_t<LORA != 0, GemmLoraArgs, GemmArgs> p) {
+    static_assert(LORA == 0 || (FP8 && EPI != GF_EPI_VT32), "the adapter epilogue exists beside the fp8 Linear only");
     constexpr unsigned ESZ = FP8 ? 1u : 2u;    // bytes per operand element
     extern __shared__ __attribute__((aligned(16))) char smem[];
     GF_LDS char* lds = (GF_LDS char*)smem;
@@ -761,7 +812,7 @@ __global__ __launch_bounds__(A4_THREADS, 1) void gemm_a4_kernel(const GemmArgs p
     // epilogue does not open with an exposed L2 round trip
     u16x4 bpre[8];
     u16x8 gpre = {0, 0, 0, 0, 0, 0, 0, 0};
-    {
+    if constexpr (LORA == 0) {   // (LORA: behind the K loop, with the adapter's fragments)
         const int fq_ = lane >> 4;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -780,7 +831,7 @@ __global__ __launch_bounds__(A4_THREADS, 1) void gemm_a4_kernel(const GemmArgs p
     }
     // fp8: the activation scales of this lane's eight rows (one per 16-row block), requested before the K loop as well
     float rsc[FP8 ? 8 : 1];
-    if constexpr (FP8 && EPI != GF_EPI_VT32) {
+    if constexpr (FP8 && EPI != GF_EPI_VT32 && LORA == 0) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) rsc[i] = p.row_scale[min(m0 + wm * 128 + i * 16 + (lane & 15), p.M - 1)];
     }
@@ -798,8 +849,38 @@ __global__ __launch_bounds__(A4_THREADS, 1) void gemm_a4_kernel(const GemmArgs p
     // fragment registers are free now): its HBM latency passes under the accumulator conversion below.  Loading it inside the
     // store loop, four pieces in flight, cost the three residual GEMMs of a block 0.12-0.17 ms each (D->D: 1.36 -> 1.2x ms).
     constexpr bool HAS_R = EPI == GF_EPI_BIAS_GATE_RESID || EPI == GF_EPI_BIAS_RESID || EPI == GF_EPI_BIAS_MUL;
+    // LORA: the adapter's fragments are requested first instead — 16 bytes per lane, fragment and chunk of 32 rank columns: row
+    // 16 i + frow of t (i < 8), row 16 j + frow of up (j < 8), rank columns 32 ch + 8 fq .. + 7; rows past M / N are +0 — and the
+    // residual pieces follow once the adapter's products below have let go of those 64 LORA registers (both sets at once do not fit)
+    u16x8 tfr[LORA ? 8 : 1][LORA ? LORA : 1], ufr[LORA ? 8 : 1][LORA ? LORA : 1];
+    int lane_e = lane;   // LORA: the lane index as the epilogue's loads see it (below)
+    if constexpr (LORA != 0) {
+        // the empty statement makes the addresses below values of the epilogue: computed ahead of the K loop they would have to live
+        // through it in the 119 VGPRs the loop leaves alone, and spill.  For the same reason this kernel asks for its bias, gate and row
+        // scales here (the same expressions as ahead of the loop): their latency passes with the fragments'.
+        asm volatile("" : "+v"(lane_e));
+        const int frow_e = lane_e & 15, fq_e = lane_e >> 4;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int n = n0 + wn * 128 + j * 16 + fq_e * 4;
+            bpre[j] = (p.bias && n < p.N) ? *reinterpret_cast<const u16x4*>(p.bias + n) : u16x4{0, 0, 0, 0};
+        }
+        const int ng = n0 + wn * 128 + frow_e * 8;
+        if (EPI == GF_EPI_BIAS_GATE_RESID && ng < p.N) gpre = *reinterpret_cast<const u16x8*>(p.gate + ng);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) rsc[i] = p.row_scale[min(m0 + wm * 128 + i * 16 + frow_e, p.M - 1)];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int mt = m0 + wm * 128 + i * 16 + frow_e, nu = n0 + wn * 128 + i * 16 + frow_e;
+#pragma unroll
+            for (int ch = 0; ch < LORA; ++ch) {
+                tfr[i][ch] = mt < p.M ? *reinterpret_cast<const u16x8*>(p.T + (long)mt * p.ldt + ch * 32 + fq_e * 8) : u16x8{0, 0, 0, 0, 0, 0, 0, 0};
+                ufr[i][ch] = nu < p.N ? *reinterpret_cast<const u16x8*>(p.U + (long)nu * p.ld_up + ch * 32 + fq_e * 8) : u16x8{0, 0, 0, 0, 0, 0, 0, 0};
+            }
+        }
+    }
     u16x8 rres[HAS_R ? 32 : 1];
-    if constexpr (HAS_R) {
+    if constexpr (HAS_R && LORA == 0) {
         const int nr = n0 + wn * 128 + (lane & 15) * 8;
 #pragma unroll
         for (int it = 0; it < 32; ++it) {
@@ -825,6 +906,8 @@ __global__ __launch_bounds__(A4_THREADS, 1) void gemm_a4_kernel(const GemmArgs p
         constexpr int j = decltype(j_c)::value;
         const int n = n0 + wn * 128 + j * 16 + fq * 4;
         const float bv[4] = {bf2f(bpre[j][0]), bf2f(bpre[j][1]), bf2f(bpre[j][2]), bf2f(bpre[j][3])};   // zeros where there is no bias
+        f32x4 dl[LORA ? 8 : 1];   // LORA: the adapter's products of column block j, fragment i in dl[i]
+        if constexpr (LORA != 0) a4_lora_mfma<LORA>(dl, ufr[j], tfr);
         gf_static_for<0, 8>([&](auto i_c) {
             constexpr int i = decltype(i_c)::value;
             constexpr int A0 = (i * 8 + j) * 4;
@@ -832,6 +915,13 @@ __global__ __launch_bounds__(A4_THREADS, 1) void gemm_a4_kernel(const GemmArgs p
             if constexpr (FP8 && EPI != GF_EPI_VT32) {   // x scale_a of the row, + bias: the same expression as the 8-wave fp8 kernel (gemm_kernel<EPI, true>)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) y[r] = y[r] * rsc[i] + bv[r];
+            }
+            if constexpr (LORA != 0) {   // lora_kernel's three roundings on y0 = bf16(y), in registers
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float s = rbf(p.scale * rbf(dl[i][r]));
+                    y[r] = rbf(rbf(y[r]) + s);
+                }
             }
             if constexpr (EPI == GF_EPI_VT32) {   // bias of the ROW (output feature); key columns that do not exist are zero
                 const float bm = bf2f(bpre[i][0]);       // requested before the K loop (0 where there is no bias / no row)
@@ -868,6 +958,18 @@ __global__ __launch_bounds__(A4_THREADS, 1) void gemm_a4_kernel(const GemmArgs p
             *(GF_LDS u32x2*)(ep + row * 256 + slot * 8) = pk;
         });
     });
+    if constexpr (HAS_R && LORA != 0) {   // the same 32 pieces, requested behind the adapter's products (see above)
+        const int nr = n0 + wn * 128 + (lane_e & 15) * 8;
+#pragma unroll
+        for (int it = 0; it < 32; ++it) {
+            const int mr = m0 + wm * 128 + it * 4 + (lane_e >> 4);
+            if (mr < p.M && nr < p.N) {
+                rres[it] = __builtin_nontemporal_load(reinterpret_cast<const u16x8*>(p.R + (long)mr * p.ldr + nr));
+            } else {
+                rres[it] = u16x8{0, 0, 0, 0, 0, 0, 0, 0};
+            }
+        }
+    }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // wave-private image: LDS is in order, no barrier needed
     {
         const int cc = lane & 15;                 // 16-byte chunk of the 256-byte row segment
@@ -907,17 +1009,17 @@ __global__ __launch_bounds__(A4_THREADS, 1) void gemm_a4_kernel(const GemmArgs p
     }
 }
 
-template <int EPI, bool FP8 = false>
-int launch_gemm_a4(const GemmArgs& a0, hipStream_t stream) {
-    GemmArgs a = a0;
+template <int EPI, bool FP8 = false, int LORA = 0>
+int launch_gemm_a4(const std::conditional_t<LORA != 0, GemmLoraArgs, GemmArgs>& a0, hipStream_t stream) {
+    auto a = a0;
     {
         // an XCD runs 32 consecutive tiles of the order = group_m row tiles x 32 / group_m column tiles: 8 x 4 and 4 x 8 both stage
         // 12 operand slices per K step; with the long K loop of F->D (K = 13824) 4 x 8 measured +1.6 %, at K = 5120 8 x 4 +1-2 %
         const int g = gf_options().a4_group_m.load(std::memory_order_relaxed);
         a.group_m = g > 0 ? g : (a.K * (FP8 ? 1 : 2) >= 16384 ? 4 : GROUP_M);   // by the K loop's length in bytes per row
     }
-    return gf_launch_lds<gemm_a4_kernel<EPI, FP8>>("gf_gemm", GF_ATTR_MSG_BYTES, FP8 ? "gf_gemm_fp8" : "gf_gemm_bf16", dim3((unsigned)(a.tiles_m * a.tiles_n)),
-                                                   dim3(A4_THREADS), GEMM_LDS, stream, a);
+    return gf_launch_lds<gemm_a4_kernel<EPI, FP8, LORA>>("gf_gemm", GF_ATTR_MSG_BYTES, LORA ? "gf_gemm_fp8_lora" : FP8 ? "gf_gemm_fp8" : "gf_gemm_bf16",
+                                                         dim3((unsigned)(a.tiles_m * a.tiles_n)), dim3(A4_THREADS), GEMM_LDS, stream, a);
 }
 
 template <int EPI, bool FP8>
@@ -1002,10 +1104,11 @@ GemmArgs gemm_args(const void* A, int64_t lda, const void* W, int64_t ldw, const
 
 }  // namespace
 
-static int gemm_dispatch(bool fp8, const void* A, int64_t lda, const void* W, int64_t ldw, const float* row_scale,
-                         const void* bias, void* C, int64_t ldc, int64_t M, int64_t N, int64_t K, int epilogue,
-                         const void* resid, int64_t ldr, const void* gate, void* stream) {
-    const char* fn = fp8 ? "gf_gemm_fp8" : "gf_gemm_bf16";
+// What gf_gemm_bf16 / gf_gemm_fp8 / gf_gemm_fp8_lora ask of the product's own operands, in `fn`'s name (the epilogue's number is
+// asked by the caller: behind the zero-size return)
+static int gemm_check_operands(const char* fn, bool fp8, const void* A, int64_t lda, const void* W, int64_t ldw, const float* row_scale,
+                               const void* bias, void* C, int64_t ldc, int64_t M, int64_t N, int64_t K, int epilogue, const void* resid,
+                               int64_t ldr, const void* gate) {
     const int bke = fp8 ? 128 : 64, lal = fp8 ? 16 : 8;
     GF_CHECK_ARG(A && W && C, "%s: null A/W/C", fn);
     GF_CHECK_ARG(M >= 0 && N > 0 && K > 0, "%s: bad sizes M=%ld N=%ld K=%ld", fn, (long)M, (long)N, (long)K);
@@ -1022,6 +1125,14 @@ static int gemm_dispatch(bool fp8, const void* A, int64_t lda, const void* W, in
                  "%s: residual epilogue needs an aligned resid with ldr >= N", fn);
     GF_CHECK_ARG(epilogue != GF_EPI_BIAS_GATE_RESID || (gate && gf_aligned16(gate)),
                  "%s: gate epilogue needs an aligned gate vector", fn);
+    return GF_OK;
+}
+
+static int gemm_dispatch(bool fp8, const void* A, int64_t lda, const void* W, int64_t ldw, const float* row_scale,
+                         const void* bias, void* C, int64_t ldc, int64_t M, int64_t N, int64_t K, int epilogue,
+                         const void* resid, int64_t ldr, const void* gate, void* stream) {
+    const char* fn = fp8 ? "gf_gemm_fp8" : "gf_gemm_bf16";
+    if (const int rc = gemm_check_operands(fn, fp8, A, lda, W, ldw, row_scale, bias, C, ldc, M, N, K, epilogue, resid, ldr, gate)) return rc;
     if (M == 0) return GF_OK;
     // after the zero-size return: an empty product has always been accepted whatever its epilogue
     GF_CHECK_ARG(epilogue >= GF_EPI_BIAS && epilogue <= GF_EPI_BIAS_MUL, "%s: unknown epilogue %d", fn, epilogue);
@@ -1044,6 +1155,51 @@ extern "C" GF_API int gf_gemm_fp8(const void* A8, int64_t lda, const void* W8, i
                                   const void* bias, void* C, int64_t ldc, int64_t M, int64_t N, int64_t K, int epilogue,
                                   const void* resid, int64_t ldr, const void* gate, void* stream) {
     return gemm_dispatch(true, A8, lda, W8, ldw, row_scale, bias, C, ldc, M, N, K, epilogue, resid, ldr, gate, stream);
+}
+
+// gf_gemm_fp8 with one attached LoRA adapter in its epilogue (gemm_a4_kernel<EPI, true, rank_pad / 32>): the 4-wave kernel's shapes
+// only — the conditions launch_gemm<EPI, true> sends a product there under, with dense rows (lda = ldw = K) for the staging bound —
+// and the padded ranks the epilogue's registers hold without a spill.
+constexpr int A4_LORA_MAX_RANK_PAD = 64;
+
+extern "C" GF_API int gf_gemm_fp8_lora_ok(int64_t M, int64_t N, int64_t K, int64_t rank_pad) {
+    if (gf_options().prefer_8wave.load(std::memory_order_relaxed) != 0) return 0;
+    if (M < 512 || M >= (1 << 30) || N <= 0 || N >= (1 << 30) || N % 8 != 0 || K <= 0 || K % 128 != 0) return 0;
+    if (256L * K + K >= (1L << 31)) return 0;
+    return rank_pad >= 32 && rank_pad <= A4_LORA_MAX_RANK_PAD && rank_pad % 32 == 0;
+}
+
+extern "C" GF_API int gf_gemm_fp8_lora(const void* A8, int64_t lda, const void* W8, int64_t ldw, const float* row_scale, const void* bias,
+                                       const void* t, int64_t ldt, const void* up, int64_t ld_up, int64_t rank_pad, float scale, void* out,
+                                       int64_t ldo, int64_t M, int64_t N, int64_t K, int epilogue, const void* resid, int64_t ldr,
+                                       const void* gate, void* stream) {
+    const char* fn = "gf_gemm_fp8_lora";
+    if (const int rc = gemm_check_operands(fn, true, A8, lda, W8, ldw, row_scale, bias, out, ldo, M, N, K, epilogue, resid, ldr, gate)) return rc;
+    GF_CHECK_ARG(epilogue >= GF_EPI_BIAS && epilogue <= GF_EPI_BIAS_MUL, "%s: unknown epilogue %d", fn, epilogue);
+    GF_CHECK_ARG(t && up, "%s: null t/up", fn);
+    GF_CHECK_ARG(rank_pad >= 32 && rank_pad <= 256 && rank_pad % 32 == 0, "%s: rank_pad=%lld must be a multiple of 32 in 32..256", fn,
+                 (long long)rank_pad);
+    GF_CHECK_ARG(ldt % 8 == 0 && ld_up % 8 == 0 && ldt >= rank_pad && ld_up >= rank_pad,
+                 "%s: ldt / ld_up must be multiples of 8 and cover the padded rank", fn);
+    GF_CHECK_ARG(gf_aligned16(t) && gf_aligned16(up), "%s: 16-byte alignment of t / up required", fn);
+    GF_CHECK_ARG(scale == scale && scale - scale == 0.f, "%s: scale must be finite", fn);
+    GF_CHECK_ARG(gf_gemm_fp8_lora_ok(M, N, K, rank_pad) && 256L * lda + K < (1L << 31) && 256L * ldw + K < (1L << 31),
+                 "%s: M=%lld N=%lld K=%lld rank_pad=%lld is outside the fused kernel's shapes (gf_gemm_fp8_lora_ok: the 4-wave kernel, M >= "
+                 "512, rank_pad <= %d, prefer_8wave off): run gf_gemm_fp8 and gf_lora_up",
+                 fn, (long long)M, (long long)N, (long long)K, (long long)rank_pad, A4_LORA_MAX_RANK_PAD);
+    GemmLoraArgs a;
+    static_cast<GemmArgs&>(a) = gemm_args(A8, lda, W8, ldw, row_scale, bias, out, ldo, resid, ldr, gate, M, N, K);
+    a.T = (const u16*)t;
+    a.U = (const u16*)up;
+    a.ldt = ldt;
+    a.ld_up = ld_up;
+    a.scale = scale;
+    hipStream_t s = (hipStream_t)stream;
+    return gf_dispatch<GF_EPI_BIAS, GF_EPI_BIAS_GELU_TANH, GF_EPI_BIAS_GATE_RESID, GF_EPI_BIAS_RESID, GF_EPI_BIAS_SILU, GF_EPI_BIAS_MUL>(
+        epilogue, [&](auto e) {
+            constexpr int E = decltype(e)::value;
+            return rank_pad == 32 ? launch_gemm_a4<E, true, 1>(a, s) : launch_gemm_a4<E, true, 2>(a, s);
+        });
 }
 
 // The V projection of a self-attention written directly as kernel 3's operand: vt[n][pos(s)] = bf16(sum_k x[s,k] w[n,k] + bias[n]),

@@ -195,10 +195,13 @@ def fp8_weight_t(lin: nn.Linear):
 
 class QuantizedInput:
     """A quantised activation shared by the GEMMs that read the same input: `kind` "fp8" — `data` e4m3 bytes, `scale` fp32 per row;
-    "fp4" — MXFP4, `data` packed e2m1 codes, `scale` E8M0 bytes (what ops.layernorm_modulate_mxfp4 / ops.gemm_mxfp4_q4 return)."""
+    "fp4" — MXFP4, `data` packed e2m1 codes, `scale` E8M0 bytes (what ops.layernorm_modulate_mxfp4 / ops.gemm_mxfp4_q4 return).
+    `x2`: under lora.set_beside_fp8(True), the bf16 tensor an fp8 input was quantised from, when it was built from one (None otherwise):
+    what the LoRA adapters beside an fp8 layer read."""
 
     def __init__(self, x2=None, data=None, scale=None, kind="fp8"):
         self.kind = kind
+        self.x2 = x2 if kind == "fp8" and lora.beside_fp8() else None     # (switch off: the bf16 tensor's lifetime is what it was)
         self.data, self.scale = getattr(ops, _QUANT[kind][2])(x2) if x2 is not None else (data, scale)
 
     @classmethod
@@ -216,9 +219,12 @@ def linear(x2, lin: nn.Linear, epilogue=ops.EPI_BIAS, resid=None, gate=None, out
     for the layer; a QuantizedInput of the layer's kind reuses one quantisation for several layers, one of another kind is refused.
     out=QuantizedInput (the class): an fp4 layer's result as the next one's input, quantised in the GEMM's epilogue (ops.gemm_mxfp4_q4).
     A bf16 layer with attached LoRA adapters of non-zero strength (lora.attach) runs its GEMM with EPI_BIAS, then per adapter
-    ops.gemm for t = x down^T and ops.lora_up, the last one with the caller's epilogue, resid, gate and out."""
+    ops.gemm for t = x down^T and ops.lora_up, the last one with the caller's epilogue, resid, gate and out.  An enable_fp8 layer with
+    live adapters is refused unless lora.set_beside_fp8 is on: then _linear_fp8_lora runs it."""
     kind, given = precision(lin), getattr(x2, "kind", "bf16")
     adapters = lora.live(lin)
+    if adapters and kind == "fp8" and lora.beside_fp8():
+        return _linear_fp8_lora(x2, lin, adapters, given, epilogue, resid, gate, out)
     if adapters:
         if kind != "bf16":
             raise GoalForceError(f"linear: an attached LoRA adapter ({adapters[0].name!r}) on an enable_{kind} layer is refused: use the "
@@ -248,6 +254,33 @@ def linear(x2, lin: nn.Linear, epilogue=ops.EPI_BIAS, resid=None, gate=None, out
         return QuantizedInput(None, *ops.gemm_mxfp4_q4(q.data, q.scale, *w, lin.bias, epilogue=epilogue), kind="fp4")
     gemm, w = (ops.gemm_mxfp4, w) if kind == "fp4" else (ops.gemm_fp8, (w,))
     return gemm(q.data, q.scale, *w, lin.bias, epilogue=epilogue, resid=resid, gate=gate, out=out)
+
+
+def _linear_fp8_lora(x2, lin, adapters, given, epilogue, resid, gate, out):
+    """linear() on an enable_fp8 layer with live adapters under lora.set_beside_fp8: the reference's AutoWrappedLinear.forward
+    (VRAM:168-187) — the fp8 product of the quantised x plus every adapter on the bf16 x.  One adapter: ops.gemm_fp8_lora (one launch
+    where gf_gemm_fp8_lora runs).  Several: ops.gemm_fp8(EPI_BIAS), then ops.lora_up per adapter in place as the bf16 route chains them,
+    the last with the caller's epilogue, resid, gate and out (each adapter's update is rounded into the running bf16 sum, which only
+    the materialised y0 can carry)."""
+    name = adapters[0].name
+    if out is QuantizedInput or given not in ("bf16", "fp8"):
+        raise GoalForceError(f"linear: a QuantizedInput was handed to or asked of a layer with an attached LoRA adapter "
+                             f"({name!r}): attached adapters run on bf16 activations only")
+    q = x2 if given == "fp8" else QuantizedInput(x2)
+    xb = q.x2
+    if xb is None:
+        raise GoalForceError(f"linear: the fp8 QuantizedInput handed to a layer with an attached LoRA adapter ({name!r}) carries no "
+                             "bf16 source (QuantizedInput.x2): the adapter reads the unquantised activation — build it from the bf16 tensor")
+    w8 = weight_copy(lin, "fp8")
+    ts = [ops.gemm(xb, ad.on(q.data.device).down) for ad in adapters]
+    if len(adapters) == 1:
+        ad = adapters[0]
+        return ops.gemm_fp8_lora(q.data, q.scale, w8, lin.bias, ts[0], ad.up, ad.alpha, epilogue=epilogue, resid=resid, gate=gate, out=out)
+    y = ops.gemm_fp8(q.data, q.scale, w8, lin.bias)
+    for ad, t in zip(adapters[:-1], ts[:-1]):
+        ops.lora_up(y, t, ad.up, ad.alpha, out=y)
+    ad = adapters[-1]
+    return ops.lora_up(y, ts[-1], ad.up, ad.alpha, epilogue=epilogue, resid=resid, gate=gate, out=y if out is None else out)
 
 
 def enable_fp8(module: nn.Module, enabled=True):
@@ -342,8 +375,12 @@ def refuse_training(block: "DiTBlock", fp8_frozen: bool = False):
         if any(precision(m, (kind,)) == kind for m in block.modules()) and not (kind == "fp8" and fp8_frozen):
             raise GoalForceError(f"training through an enable_{kind} block is refused: call enable_{kind}(module, False) first")
     if fp8_frozen and any(precision(m, ("fp8",)) == "fp8" for m in block.modules()):
-        what = next((f"the trainable parameter {n}" for n, p in block.named_parameters() if p.requires_grad), None) or next(
-            (f"a live LoRA adapter ({n}: {lora.live(m)[0].name!r})" for n, m in block.named_modules() if lora.live(m)), None)
+        # lora.set_beside_fp8: live TRAINABLE adapters are differentiated beside the frozen fp8 layers (their parameters are the only
+        # ones that may ask for a gradient); a frozen attached adapter meets the refusal below, as on a bf16 block
+        beside = lora.beside_fp8()
+        own = {id(p) for _, m in block.named_modules() for ad in lora.live(m) if ad.trainable for p in (ad.down, ad.up)} if beside else ()
+        what = next((f"the trainable parameter {n}" for n, p in block.named_parameters() if p.requires_grad and id(p) not in own), None) or next(
+            (f"a live LoRA adapter ({n}: {lora.live(m)[0].name!r})" for n, m in block.named_modules() if lora.live(m) and not beside), None)
         if what is not None:
             raise GoalForceError(f"training through an enable_fp8 block is open to frozen blocks only (no weight gradient exists on the fp8 "
                                  f"kernels): this block has {what}: freeze it, or call enable_fp8(module, False) first")
@@ -691,6 +728,12 @@ class DiTBlock(nn.Module):
         kind = precision(reader)
         if kind == "bf16" or (kind == "fp4" and not ops.option("fp4_fused")):
             return ops.layernorm_modulate(x2, eps=self.eps, out=out, **kw)
+        if kind == "fp8" and lora.beside_fp8():
+            # an adapter beside the reader — or beside k / v, which read the q projection's input — reads the bf16 row: the two kernels
+            # the fused producer stands for (the same codes and scales), the QuantizedInput keeping its source
+            sa = self.self_attn
+            if any(lora.live(m) for m in ((sa.q, sa.k, sa.v) if reader is sa.q else (reader,))):
+                return QuantizedInput(ops.layernorm_modulate(x2, eps=self.eps, **kw))
         return QuantizedInput.layernorm(x2, kind, eps=self.eps, **kw)
 
     def forward(self, x, context, t_mod, freqs, context_kv=None, out=None, sp=None, keep=None, self_attn_memo=None,

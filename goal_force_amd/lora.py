@@ -7,7 +7,8 @@
   bf16 roundings torch makes there.  Irreversible, and a second call stacks on the first, as in the reference.
 * `attach(module, state_dict, alpha, name)` / `detach` / `set_strength`: the adapter stays beside the layer and dit.linear adds
   peft's unmerged forward, result + lora_B(lora_A(x)) * scaling, per call (ops.gemm for x down^T, ops.lora_up).  The masters are
-  never written; detached or at strength 0 the layer runs its single launch again, bit for bit.  bf16 layers only.
+  never written; detached or at strength 0 the layer runs its single launch again, bit for bit.  bf16 layers only — and, under
+  `set_beside_fp8(True)`, enable_fp8 layers: the fp8 product plus the adapter on the bf16 input (ops.gemm_fp8_lora; VRAM:168-187).
 
 * `add_trainable(module, target_modules, rank, alpha, name)` restates `add_lora_to_model` (src/goal_force/utils.py:450-459: peft's
   LoraConfig + inject_adapter_in_model): a TRAINABLE adapter beside every Linear peft's rule matches, `lora_A` kaiming-uniform,
@@ -30,6 +31,24 @@ from ._lib import GoalForceError
 
 MAX_RANK = 256       # gf_lora_merge / gf_lora_up
 RANK_TILE = 32       # attach pads the rank to a multiple of this (one MFMA's K; it also gives ops.gemm its N % 8)
+
+
+_BESIDE_FP8 = [False]
+
+
+def set_beside_fp8(on) -> bool:
+    """Open (or close) attached adapters beside enable_fp8 Linears; returns the previous setting.  Off — the default — every fp8
+    combination is refused by name as ever.  On: attach / add_trainable take a Linear that carries an fp8 copy (fp4 stays refused),
+    dit.linear runs the reference's AutoWrappedLinear.forward on it (VRAM:168-187) — the fp8 product of the quantised input plus the
+    adapters on the bf16 input (ops.gemm_fp8_lora) — and, with training.set_fp8_frozen, the tape takes a frozen fp8 block whose only
+    trainable things are live trainable adapters (dit.refuse_training).  A process-wide switch like training.set_fp8_frozen; no
+    environment variable is read."""
+    prev, _BESIDE_FP8[0] = _BESIDE_FP8[0], bool(on)
+    return prev
+
+
+def beside_fp8() -> bool:
+    return _BESIDE_FP8[0]
 
 
 def name_dict(state_dict):
@@ -169,7 +188,7 @@ def _check_host(what, mod_name, lin, hosted, own_linears, name):
         raise GoalForceError(f"{what}: {mod_name!r} is not a Linear of a DiT block (q / k / v / o, ffn.0, ffn.2), the layers an "
                              "attached adapter runs on: use the merged form (pipe.load_lora) for it")
     kind = dit.precision(lin)
-    if kind != "bf16":
+    if kind != "bf16" and not (kind == "fp8" and beside_fp8()):
         raise GoalForceError(f"{what}: {mod_name!r} carries an enable_{kind} weight copy: attached adapters run on bf16 layers "
                              "only (use the merged form, pipe.load_lora, with quantised layers)")
     if any(ad.name == name for ad in adapters(lin)):
@@ -283,6 +302,7 @@ def add_trainable(module: nn.Module, target_modules, rank, alpha=None, name="def
     kaiming_uniform_(a=sqrt 5) — drawn with torch's generator in fp32 and rounded to bf16 (peft's distribution, not its draws);
     lora_B zero.  Only bf16 Linears of DiT / ControlNet blocks take one (lora.attach's rule); a target that matches nothing is an
     error by name.  Nothing else is frozen here: the caller decides what else trains.  Returns how many adapters were added."""
+    from . import dit
     what = "lora.add_trainable"
     rank = int(rank)
     if not 1 <= rank <= MAX_RANK:
@@ -302,6 +322,11 @@ def add_trainable(module: nn.Module, target_modules, rank, alpha=None, name="def
             raise GoalForceError(f"{what}: {mod_name!r}: the weight must be bf16, got {w.dtype}")
         if w.shape[0] % 64 or w.shape[1] % 64:       # x down^T and dy up sum over them on the GEMM (its K step)
             raise GoalForceError(f"{what}: {mod_name!r} is {tuple(w.shape)}: a trainable adapter takes features that are multiples of 64")
+        # under set_beside_fp8 the layer may get its fp8 copy after this call (scripts/train.py: add_lora, then enable_fp8_training):
+        # asked whatever the layer's precision is now.  dX = dY W8 sums over out_features on the fp8 GEMM, whose K step is 128.
+        if beside_fp8() and (w.shape[0] % 128 or w.shape[1] % 128):
+            raise GoalForceError(f"{what}: {mod_name!r} is {tuple(w.shape)}: under lora.set_beside_fp8 a trainable adapter takes features "
+                                 "that are multiples of 128 (the fp8 GEMMs' K step, forward and dX)")
     rp = -(-rank // RANK_TILE) * RANK_TILE
     for mod_name, lin in matched:
         n_out, k_in = lin.weight.shape

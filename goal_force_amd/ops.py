@@ -16,7 +16,7 @@ from ._lib import (EPI_BIAS, EPI_BIAS_GATE_RESID, EPI_BIAS_GELU_TANH, EPI_BIAS_M
 
 __all__ = [
     "modulation", "layernorm_modulate", "rmsnorm_rope", "gate_residual", "gemm", "flash_attn", "flash_attn_sparse", "BlockMap", "block_means", "block_means_coherence", "block_map_scores", "block_map_select", "block_map_from_qk", "patchify_im2col", "unpatchify",
-    "cfg_euler_step", "act", "add", "sub", "rel_l1", "force_map", "lora_merge", "lora_up", "lora_grad",
+    "cfg_euler_step", "act", "add", "sub", "rel_l1", "force_map", "lora_merge", "lora_up", "lora_grad", "gemm_fp8_lora",
     "EPI_BIAS", "EPI_BIAS_GELU_TANH", "EPI_BIAS_GATE_RESID", "EPI_BIAS_RESID", "EPI_BIAS_SILU", "EPI_BIAS_MUL",
 ]
 
@@ -404,10 +404,11 @@ VT_MIN_KV = 2048  # key sequences at least this long go through the pre-transpos
 #                              folded value table, dit.CrossAttention.fold_ok),
 #                fp4_fused (False: the FFN of an enable_fp4 block as five launches — LayerNorm, quant_mxfp4, GEMM, quant_mxfp4, GEMM —
 #                           instead of three with the quantisation inside the LayerNorm and the GELU GEMM's epilogue; the same bits)
+#                fp8_lora_fused (False: gemm_fp8_lora as gemm_fp8 + lora_up, two launches, where gf_gemm_fp8_lora would run; the same bits)
 _LIB_DEFAULTS = {"prefer_8wave": 0, "a4_stagger": 2, "a4_group_m": 0, "conv_nb": 0, "conv_gather": 0, "conv_direct": 1, "vae_rms3": 1,
                  "attn_fixed_max": 1}
 _OPT = {"attn_k3": True, "vt_from_gemm": True, "conv_padded": True, "fold_pad_keys": True, "attn_q_prescale": True, "vae_attn_offset": True,
-        "fold_cross_o": True, "fp4_fused": True}
+        "fold_cross_o": True, "fp4_fused": True, "fp8_lora_fused": True}
 
 
 def option(name: str) -> bool:
@@ -1679,6 +1680,45 @@ def gemm_fp8(a8, row_scale, w8, bias=None, epilogue=EPI_BIAS, resid=None, gate=N
     if row_scale is None:
         raise GoalForceError("gemm_fp8.row_scale: required")
     return _gemm(a8, w8, row_scale, bias, epilogue, resid, gate, out)
+
+
+FP8_LORA_RANK_PADS = (32, 64)     # the padded ranks gf_gemm_fp8_lora holds in its epilogue's registers
+
+
+def gemm_fp8_lora_ok(M, N, K, rank_pad) -> bool:
+    """Where gf_gemm_fp8_lora runs (gf_gemm_fp8_lora_ok, asked of the library: the option prefer_8wave is part of the answer)."""
+    return bool(_lib.load().gf_gemm_fp8_lora_ok(M, N, K, rank_pad))
+
+
+def gemm_fp8_lora(a8, row_scale, w8, bias, t, up, scale, epilogue=EPI_BIAS, resid=None, gate=None, out=None):
+    """out[M,N] = epilogue(bf16(y0 + bf16(fp32(scale) * bf16(t[M,R] @ up[N,R]^T))), resid, gate) with y0 = bf16((a8 @ w8^T) * row_scale
+    + bias): an fp8 Linear with one attached adapter on the bf16 input (t = gemm(x, down_pad)), the reference's
+    AutoWrappedLinear.forward (VRAM:168-187).  One launch, gf_gemm_fp8_lora, where gf_gemm_fp8_lora_ok says so and
+    option("fp8_lora_fused") is on; otherwise gemm_fp8(EPI_BIAS) into a new tensor and lora_up: the same bits by contract.
+    `out` may be resid (None: a new tensor)."""
+    op = "gemm_fp8_lora"
+    if row_scale is None:
+        raise GoalForceError(f"{op}.row_scale: required")
+    av, M, K, lda, N, ldw = _linear_operands(a8, w8, row_scale)
+    R = t.shape[-1]
+    tv, ldt = _rows_like(t, f"{op}.t", M, R)
+    Nu, ld_up = _weight(up, f"{op}.up", R)
+    if Nu != N:
+        raise GoalForceError(f"{op}.up: expected [{N}, {R}], got {tuple(up.shape)}")
+    if R % 32 or not 32 <= R <= LORA_MAX_RANK:
+        raise GoalForceError(f"{op}: padded rank {R}: expected a multiple of 32 in 32..{LORA_MAX_RANK}")
+    scale = _lora_scale(op, "scale", scale)
+    if not (option("fp8_lora_fused") and gemm_fp8_lora_ok(M, N, K, R) and 256 * max(lda, ldw) + K < 2 ** 31):
+        y0 = gemm_fp8(a8, row_scale, w8, bias)
+        return lora_up(y0, t, up, scale, epilogue=epilogue, resid=resid, gate=gate, out=y0 if out is None else out)
+    if out is None:
+        out = torch.empty((M, N), dtype=_BF16, device=a8.device)
+    ov, ldo, resid, ldr = _gemm_result_operands(op, M, N, out, resid, gate, bias)
+    with _timed(PROFILE_GEMM, M, N, K, int(epilogue)):
+        _lib.check(_lib.load().gf_gemm_fp8_lora(_ptr(av), lda, _ptr(w8), ldw, _ptr(row_scale), _ptr(bias), _ptr(tv), ldt, _ptr(up), ld_up,
+                                                R, scale, _ptr(ov), ldo, M, N, K, int(epilogue), _ptr(resid), ldr, _ptr(gate),
+                                                _stream(a8)), "gf_gemm_fp8_lora")
+    return out
 
 
 # ---------------------------------------------------------------------------------- MXFP4 Linear (goalforce.h; no reference counterpart)

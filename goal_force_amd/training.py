@@ -365,10 +365,15 @@ class DiTBlockFn(torch.autograd.Function):
         mod = ops.modulation(block.modulation, t_mod.contiguous(), onep_mask=0b010010)
         need_h1 = wide is None or any(need[f"self_attn.{n}.weight"] or f"self_attn.{n}" in by_layer for n in "qkv")
         fp8 = precision(sa.q) == "fp8"       # a frozen enable_fp8 block: one quantisation of h1 for q / k / v, as the forward's (never bf16 in HBM)
-        if fp8 and need_h1:
+        h1b = None                           # h1 as bf16: what the adapters of q / k / v read
+        if fp8 and need_h1 and any(f"self_attn.{n}" in by_layer for n in "qkv"):
+            # adapters beside the fp8 q / k / v (lora.set_beside_fp8): h1 exists as bf16 and as its quantisation, as in the forward
+            h1b = ops.layernorm_modulate(x, scale1p=mod[1], shift=mod[0], eps=eps)
+            h1 = QuantizedInput(h1b)
+        elif fp8 and need_h1:
             h1 = QuantizedInput.layernorm(x, "fp8", scale1p=mod[1], shift=mod[0], eps=eps)
         else:
-            h1 = ops.layernorm_modulate(x, scale1p=mod[1], shift=mod[0], eps=eps) if need_h1 else None
+            h1 = h1b = ops.layernorm_modulate(x, scale1p=mod[1], shift=mod[0], eps=eps) if need_h1 else None
         if wide is not None:
             qp, kp, vv = wide["qp"], wide["kp"], wide["v"]
         else:
@@ -442,9 +447,9 @@ class DiTBlockFn(torch.autograd.Function):
             g["self_attn.norm_q.weight"] = ops.f32_to_bf16(wq_acc)
         if wk_acc is not None:
             g["self_attn.norm_k.weight"] = ops.f32_to_bf16(wk_acc)
-        dh1 = lin_bwd(dqp, h1, sa.q, "self_attn.q")
-        dh1 = ops.add(dh1, lin_bwd(dkp, h1, sa.k, "self_attn.k"))
-        dh1 = ops.add(dh1, lin_bwd(dvv, h1, sa.v, "self_attn.v"))
+        dh1 = lin_bwd(dqp, h1b, sa.q, "self_attn.q")          # (a frozen fp8 layer without an adapter reads no input here)
+        dh1 = ops.add(dh1, lin_bwd(dkp, h1b, sa.k, "self_attn.k"))
+        dh1 = ops.add(dh1, lin_bwd(dvv, h1b, sa.v, "self_attn.v"))
         dscale1, dshift1 = acc(), acc()
         dx = ops.add(d_x1, ops.layernorm_bwd(x, dh1, g=mod[1], dg_acc=dscale1, db_acc=dshift1, eps=eps))
         if need["modulation"]:    # rows: shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp (d(1+s) = ds)

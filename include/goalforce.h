@@ -705,6 +705,25 @@ GF_API int gf_gemm_fp8(const void* A8, int64_t lda, const void* W8, int64_t ldw,
                        const void* bias, void* C, int64_t ldc, int64_t M, int64_t N, int64_t K,
                        int epilogue, const void* resid, int64_t ldr, const void* gate, void* stream);
 
+/* gf_gemm_fp8_lora — an fp8 Linear with ONE attached LoRA adapter added in the GEMM's epilogue (the reference's
+ * AutoWrappedLinear.forward, VRAM:168-187: out = fp8_linear(x), then out + x @ lora_A.T @ lora_B.T on the bf16 x):
+ *     y0       = bf16( (A8 · W8^T)[m,n] * row_scale[m] + bias[n] )
+ *     out[m,n] = epi( bf16( y0 + bf16( scale * bf16( sum_j t[m,j] * up[n,j] ) ) ), resid, gate )
+ * by definition the bits of gf_gemm_fp8(..., GF_EPI_BIAS) followed by gf_lora_up(..., epilogue, resid, gate): the same K loop, the
+ * same three bf16 roundings taken in registers, the rank summed as gf_lora_up sums it (a zero fp32 accumulator, one
+ * v_mfma_f32_16x16x32_bf16 per chunk of 32 rank columns, chunks ascending); y0 is never written.  The first eleven operands and
+ * M .. stream are gf_gemm_fp8's (out [M, ldo] = its C); t [M, ldt] bf16 = bf16(x down^T), up [N, ld_up] bf16 with columns true rank ..
+ * rank_pad - 1 zero, rank_pad and scale follow gf_lora_up's contract (ldt / ld_up multiples of 8 that cover rank_pad, 16-byte aligned
+ * bases, scale finite).  out may alias resid.  It runs exactly where gf_gemm_fp8_lora_ok returns 1 — the 4-wave kernel's shapes
+ * (M >= 512, K % 128 == 0, N % 8 == 0, 256 rows of K bytes within 2^31), rank_pad 32 or 64, option prefer_8wave off; a pure function
+ * of its arguments and that option — and refuses everything else by message with out untouched: there the two launches are the route
+ * (ops.gemm_fp8_lora takes it). */
+GF_API int gf_gemm_fp8_lora_ok(int64_t M, int64_t N, int64_t K, int64_t rank_pad);
+GF_API int gf_gemm_fp8_lora(const void* A8, int64_t lda, const void* W8, int64_t ldw, const float* row_scale, const void* bias,
+                            const void* t, int64_t ldt, const void* up, int64_t ld_up, int64_t rank_pad, float scale, void* out,
+                            int64_t ldo, int64_t M, int64_t N, int64_t K, int epilogue, const void* resid, int64_t ldr,
+                            const void* gate, void* stream);
+
 /* ========================================================================
  * MXFP4 Linear — OCP Microscaling FP4 (no counterpart in the reference; off by default, dit.enable_fp4).  The format, stated once:
  *   element  e2m1, code s|ee|m: magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6 (codes 0..7), bit 3 the sign

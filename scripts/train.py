@@ -50,7 +50,7 @@ def check_args(args):
     trainable = args.trainable_models or ""
     if getattr(args, "enable_fp8_training", False):
         # the experts' blocks run fp8 and frozen (training.set_fp8_frozen: dX on the fp8 GEMM, no weight gradient); nothing of them may train
-        if args.lora_base_model is not None:
+        if args.lora_base_model is not None and not getattr(args, "lora_beside_fp8", False):
             raise NotImplementedError("--enable_fp8_training: trainable LoRA adapters run on bf16 layers only (the fp8 tape is open to frozen "
                                       "blocks: drop --lora_base_model)")
         if any(m in ("dit", "dit2") for m in trainable.split(",")):
@@ -75,6 +75,8 @@ def add_lora(pipe, args):
     if args.lora_base_model is None:
         return 0
     from goal_force_amd import lora
+    if getattr(args, "lora_beside_fp8", False):
+        lora.set_beside_fp8(True)      # before the adapters exist: they go beside Linears that carry (or will carry) an fp8 copy
     from goal_force_amd.checkpoints import load_state_dict
     model = getattr(pipe, args.lora_base_model, None)
     if model is None:
@@ -92,6 +94,8 @@ def parser():
     ap = wan_parser()
     ap.add_argument("--enable_fp8_training", default=False, action="store_true",
                     help="Run the frozen experts' blocks on the fp8 kernels, forward and backward (ControlNet training only).")
+    ap.add_argument("--lora_beside_fp8", default=False, action="store_true",
+                    help="With --enable_fp8_training: train the --lora_base_model adapters beside the frozen fp8 Linears (lora.set_beside_fp8).")
     return ap
 
 
